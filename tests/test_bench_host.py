@@ -104,3 +104,16 @@ def test_bench_rejects_world_size_other_than_gpus():
                          env=env, capture_output=True, text=True, timeout=120)
     assert out.returncode != 0
     assert '--gpus 2 but the job has 1 ranks' in out.stderr
+
+
+def test_full_option_gates_everything_but_the_timed_steps(monkeypatch):
+    """Without --full no leg beyond the timed steps is on, whatever --no-* says;
+    with it the --no-* options pick among them as before."""
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    assert a.no_cpu_baseline and a.no_band and a.no_der and a.no_extras and a.no_sparse
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--no-band', '--dump-outputs', 'd'])
+    a = bench.parse()
+    assert a.full and a.no_band and a.dump_outputs == 'd'
+    assert not (a.no_cpu_baseline or a.no_der or a.no_extras or a.no_sparse)

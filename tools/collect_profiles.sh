@@ -16,7 +16,7 @@ for c in sparse4 sparse5; do
   [ -f $D/prof_$c/run_kernel_stats.csv ] && cp $D/prof_$c/run_kernel_stats.csv $S/rocprof_kernel_stats_$c.csv
   [ -f $D/bench_under_rocprof_$c.json ] && cp $D/bench_under_rocprof_$c.json $S/
   if [ -d $D/pmc_${c}_FETCH_SIZE ]; then
-    PMC_MARKS=1 python tools/pmc_summary.py $S/pmc_traffic_$c.json "bench.py --config $c --steps 1 --warmup 0 --no-cpu-baseline (assembly, reference checks, one timed step between timing marks, isolated launches); FETCH_SIZE / WRITE_SIZE passes (KB; gfx950 FETCH counts half of wide streaming reads); per_dispatch_timed = the timed step's dispatches (first pair of timing_mark_kernel)" $D/pmc_${c}_FETCH_SIZE $D/pmc_${c}_WRITE_SIZE > /dev/null || exit 1
+    PMC_MARKS=1 python tools/pmc_summary.py $S/pmc_traffic_$c.json "bench.py --full --config $c --steps 1 --warmup 0 --no-cpu-baseline (assembly, reference checks, one timed step between timing marks, isolated launches); FETCH_SIZE / WRITE_SIZE passes (KB; gfx950 FETCH counts half of wide streaming reads); per_dispatch_timed = the timed step's dispatches (first pair of timing_mark_kernel)" $D/pmc_${c}_FETCH_SIZE $D/pmc_${c}_WRITE_SIZE > /dev/null || exit 1
   fi
 done
 if [ -d $D/pmc_dense_FETCH_SIZE ]; then

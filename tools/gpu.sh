@@ -5,12 +5,12 @@
 # Tasks:
 #   tests        -m gpu suite (verbose log) + smoke()
 #   tests:<expr> -m gpu tests matching -k <expr>
-#   bench        default bench line (dense + band + sparse + CPU baselines)
-#   bench-fast   default bench line without CPU baselines
-#   sparse4 / sparse5   bench --config sparseN (with its CPU baseline)
+#   bench        bench --full line (dense + band + sparse + CPU baselines)
+#   bench-fast   bench --full line without CPU baselines
+#   sparse4 / sparse5   bench --full --config sparseN (with its CPU baseline)
 #   rehearse     N=2 ranks on the shared device (gloo): dense+band+sparse line,
 #                and the N=1 line with an RCCL process group (GPMI_BENCH_PG=1)
-#   trace        rocprofv3 --kernel-trace --stats of bench --steps 3 --warmup 1
+#   trace        rocprofv3 --kernel-trace --stats of bench --full --steps 3 --warmup 1
 #                --no-cpu-baseline (dense+band+sparse) + the bench line it ran
 #   trace-dense  the same for the dense line only (--no-band --no-sparse): the
 #                headline syrk_kernel launches, summarised by tools/trace_summary.py
@@ -56,22 +56,22 @@ for task in "$@"; do
       run 900 $D/tests_k.log python -u -m pytest tests -m gpu -v --timeout 400 --timeout-method thread -k "${task#tests:}"
       tail -1 $D/tests_k.log ;;
     bench)
-      run 900 $D/bench.err python -u bench.py --out-json $D/bench.json
+      run 900 $D/bench.err python -u bench.py --full --out-json $D/bench.json
       python tools/bench_summary.py $D/bench.json ;;
     bench-fast)
-      run 900 $D/bench_fast.err python -u bench.py --no-cpu-baseline --out-json $D/bench_fast.json
+      run 900 $D/bench_fast.err python -u bench.py --full --no-cpu-baseline --out-json $D/bench_fast.json
       python tools/bench_summary.py $D/bench_fast.json ;;
     sparse4|sparse5)
-      run 400 $D/$task.err python -u bench.py --config $task --out-json $D/$task.json
+      run 400 $D/$task.err python -u bench.py --full --config $task --out-json $D/$task.json
       python tools/bench_summary.py $D/$task.json ;;
     rehearse)
       GPMI_BENCH_SHARE_DEVICE=1 GPMI_BENCH_BACKEND=gloo \
-        run 900 $D/n2.err python -u bench.py --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline --out-json $D/n2.json
+        run 900 $D/n2.err python -u bench.py --full --gpus 2 --steps 2 --warmup 1 --no-cpu-baseline --out-json $D/n2.json
       python tools/bench_summary.py $D/n2.json
-      GPMI_BENCH_PG=1 run 900 $D/pg1.err python -u bench.py --steps 3 --warmup 1 --no-cpu-baseline --out-json $D/pg1.json
+      GPMI_BENCH_PG=1 run 900 $D/pg1.err python -u bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --out-json $D/pg1.json
       python tools/bench_summary.py $D/pg1.json ;;
     trace)
-      run 900 $D/trace.err rocprofv3 --kernel-trace --stats -d $D/prof -o run --output-format csv -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --out-json $D/bench_under_rocprof.json
+      run 900 $D/trace.err rocprofv3 --kernel-trace --stats -d $D/prof -o run --output-format csv -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --out-json $D/bench_under_rocprof.json
       python tools/bench_summary.py $D/bench_under_rocprof.json ;;
     trace-dense)
       run 600 $D/trace_dense.err rocprofv3 --kernel-trace --stats -d $D/prof_dense -o run --output-format csv -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-band --no-sparse --no-extras --out-json $D/bench_dense_under_rocprof.json
@@ -98,7 +98,7 @@ for task in "$@"; do
     pmc-sparse4|pmc-sparse5)
       cfg=${task#pmc-}
       for c in FETCH_SIZE WRITE_SIZE; do
-        run 200 $D/pmc_${cfg}_$c.log rocprofv3 --pmc $c --kernel-trace -d $D/pmc_${cfg}_$c -o run --output-format csv -- python3 bench.py --config $cfg --steps 1 --warmup 0 --no-cpu-baseline
+        run 200 $D/pmc_${cfg}_$c.log rocprofv3 --pmc $c --kernel-trace -d $D/pmc_${cfg}_$c -o run --output-format csv -- python3 bench.py --full --config $cfg --steps 1 --warmup 0 --no-cpu-baseline
       done ;;
     trace-band)
       run 300 $D/trace_band.err rocprofv3 --kernel-trace --stats -d $D/prof_band -o run --output-format csv -- python3 tools/band_refresh_probe.py 128 1
@@ -106,7 +106,7 @@ for task in "$@"; do
       head -12 $D/band_timeline.txt ;;
     trace-sparse4|trace-sparse5)
       cfg=${task#trace-}
-      run 400 $D/trace_$cfg.err rocprofv3 --kernel-trace --stats -d $D/prof_$cfg -o run --output-format csv -- python3 bench.py --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --out-json $D/bench_under_rocprof_$cfg.json
+      run 400 $D/trace_$cfg.err rocprofv3 --kernel-trace --stats -d $D/prof_$cfg -o run --output-format csv -- python3 bench.py --full --config $cfg --steps 3 --warmup 1 --no-cpu-baseline --out-json $D/bench_under_rocprof_$cfg.json
       python tools/bench_summary.py $D/bench_under_rocprof_$cfg.json
       python tools/trace_summary.py --timed-spmm $D/prof_$cfg $D/bench_under_rocprof_$cfg.json > $D/spmm_timed_launches_$cfg.json
       cat $D/spmm_timed_launches_$cfg.json ;;
