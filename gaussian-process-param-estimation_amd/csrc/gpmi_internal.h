@@ -5,6 +5,8 @@
 #include <stdint.h>
 #include <stdlib.h>
 
+#include "gpmi_ms_sched.h"   // MS_MAXS, MsPin (HIP-free: shared with the host scheduler)
+
 #define GPMI_MAX_DIM 8     // max point dimension handled by the assembly kernel
 #define GPMI_TS 128        // tile / diagonal-block size of the blocked Cholesky
 #define GPMI_RHS_LD 16     // leading dimension (max columns) of a resident RHS block
@@ -86,16 +88,11 @@ __global__ void gram_sumsq_kernel(const double* W, int64_t ldw, const double* Td
 __global__ void matern_eval_kernel(const double* x, int64_t m, MaternParams P, double* out);
 
 // Multi-shift CG Gram state (gpmi_sparse.hip, gpmi_sparse_api.hip); device pointers.
-constexpr int MS_MAXS = 16;   // RHS columns per multi-shift block
 #ifndef GPMI_LZ_JC
 #define GPMI_LZ_JC 16
 #endif
 constexpr int LZ_JC = GPMI_LZ_JC;   // basis vectors per lz_dots_kernel launch (DCGS2 Lanczos)
 
-// A multi-shift CG batch's end state, written by the batch's last ms_tail_kernel
-// (block 0) straight into host-mapped pinned memory: the host reads it after an
-// event behind that kernel (no copy launches; round 4 copied the three fields with
-// three hipMemcpyAsync blits, ~75 us per batch with their gaps).
 // The Chronopoulos-Gear multi-shift CG (ms_cg2_update_kernel): the seed scalars,
 // double-buffered by iteration parity (every block of iteration k reads cur, block 0
 // writes nxt), and the shift state only block 0 touches.
@@ -143,14 +140,6 @@ struct MsCompactArgs {
   const int* act_src;       // [s] the old block's active flags at the compaction
   int* act;                 // [a] the compacted block's (a kept column may have stopped
                             //     since the slot the map came from was written)
-};
-
-struct MsPin {
-  int act[MS_MAXS];
-  int flag;
-  int pad;
-  double rr[MS_MAXS];
-  double bn2[MS_MAXS];   // ||b_c||^2, written by ms_init_kernel into both slots
 };
 
 // Scatter a sparse operator's CSR (original point order) into a zeroed dense

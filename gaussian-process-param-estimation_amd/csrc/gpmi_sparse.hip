@@ -14,6 +14,7 @@
 #include <stdint.h>
 
 #include "gpmi_device.h"
+#include "gpmi_sparse.h"
 
 namespace gpmi {
 
@@ -156,11 +157,6 @@ template __global__ void csr_spmm_pair_kernel<3>(const int64_t*, const int*, con
 // doubles (≈5x at cfg 5). Blocks with more than WIN_MAXM nonzeros or WIN_MAXU
 // window columns keep gathering from X (u_b = 0).
 // ---------------------------------------------------------------------------
-constexpr int WIN_ROWS = 64;
-constexpr int WIN_MAXM = 4096;
-constexpr int WIN_MAXU = 1024;
-constexpr int WIN_CS = 8;
-
 __global__ __launch_bounds__(256) void spmm_window_build_kernel(
     const int64_t* __restrict__ indptr, const int* __restrict__ indices, int64_t n,
     int* __restrict__ wcols, int* __restrict__ ucount, unsigned short* __restrict__ lidx) {
@@ -480,7 +476,7 @@ __global__ __launch_bounds__(64 * TPR) void csr_spmm_wing_kernel(
 // rank's 3 probes and 2 columns (round 6; the gather kernels they fell back to
 // made cfg 5's rank step 3x slower than the whole single-GPU step)
 #define GPMI_WING_INST(S)                                                                \
-  template __global__ void csr_spmm_wing_kernel<S, 8, 4>(                                 \
+  template __global__ void csr_spmm_wing_kernel<S, WING_U, WING_TPR>(                     \
       const int64_t*, const int*, const unsigned short*, const double*, int64_t, const int*, \
       const int*, const double*, double*, double, double*, int, unsigned long long*);
 GPMI_WING_INST(1) GPMI_WING_INST(2) GPMI_WING_INST(3) GPMI_WING_INST(4) GPMI_WING_INST(5)
@@ -488,6 +484,7 @@ GPMI_WING_INST(6) GPMI_WING_INST(7) GPMI_WING_INST(8) GPMI_WING_INST(9) GPMI_WIN
 GPMI_WING_INST(11) GPMI_WING_INST(12) GPMI_WING_INST(13) GPMI_WING_INST(14) GPMI_WING_INST(15)
 GPMI_WING_INST(16) GPMI_WING_INST(17) GPMI_WING_INST(18) GPMI_WING_INST(19) GPMI_WING_INST(20)
 #undef GPMI_WING_INST
+static_assert(WING_MAXS == 20, "instantiate csr_spmm_wing_kernel for every width");
 
 // partial[b][j][c] = sum over this block's rows of A_j[i][c] * B[i][c],
 // A_j = A + j * strideA, j = blockIdx.y; grid-stride over rows.

@@ -19,48 +19,15 @@
 #include <vector>
 
 #include "gpmi_internal.h"
+#include "gpmi_sparse.h"
+#include "gpmi_ms_sched.h"
 #include "gpmi_band.h"
 #include "../../include/gpmi.h"
 
 using namespace gpmi;
 
 namespace gpmi {
-__global__ void csr_count_kernel(const double*, int64_t, int, const double*, MaternParams, double,
-                                 double, int*);
-__global__ void csr_fill_kernel(const double*, int64_t, int, const double*, MaternParams, double,
-                                double, const int64_t*, int*, double*);
-__global__ void matern_eval_kernel(const double*, int64_t, MaternParams, double*);
-__global__ void csr_cell_count_kernel(const double*, int64_t, int, const double*, MaternParams,
-                                      double, double, const int*, const int*, const int*,
-                                      const int*, int*);
-__global__ void csr_cell_fill_kernel(const double*, int64_t, int, const double*, MaternParams,
-                                     double, double, const int*, const int*, const int*,
-                                     const int*, const int64_t*, int*, double*);
-constexpr int CELL_CAP_HOST = 512;   // = CELL_CAP (gpmi_matern.hip)
-__global__ void csr_spmm_kernel(const int64_t*, const int*, const double*, int64_t, const double*,
-                                int64_t, double*, int64_t, int, int, double);
-template <int U>
-__global__ void csr_spmm_pair_kernel(const int64_t*, const int*, const double*, int64_t,
-                                     const double*, double*, int, int, double);
-__global__ void spmm_window_build_kernel(const int64_t*, const int*, int64_t, int*, int*,
-                                         unsigned short*);
-__global__ void csr_spmm_win_kernel(const int64_t*, const int*, const unsigned short*,
-                                    const double*, int64_t, const int*, const int*, const double*,
-                                    int64_t, double*, int64_t, int, double);
-template <int S, int U, int TPR>
-__global__ void csr_spmm_wing_kernel(const int64_t*, const int*, const unsigned short*,
-                                     const double*, int64_t, const int*, const int*,
-                                     const double*, double*, double, double*, int,
-                                     unsigned long long*);
 constexpr int WING_MAX_LDS = 80 * 1024;   // two workgroups per CU
-// nonzeros in flight per thread and threads per row of csr_spmm_wing_kernel (measured:
-// 8 in flight best at cfg 5, within 0.3 us of 4 at cfg 4; 8 threads per row in
-// 512-thread blocks faster only at cfg 5 s = 11, 55 against 59 us, slower elsewhere)
-constexpr int WING_U = 8, WING_TPR = 4;
-constexpr int WIN_ROWS_HOST = 64;    // = WIN_ROWS (gpmi_sparse.hip)
-constexpr int WIN_MAXU_HOST = 1024;  // = WIN_MAXU
-constexpr int WIN_CS_HOST = 8;       // = WIN_CS
-constexpr int WING_MAXS = 20;        // widths 1 .. WING_MAXS have a window kernel
 
 // csr_spmm_wing_kernel<s> for s in [1, WING_MAXS] (index s - 1)
 template <int... I>
@@ -69,52 +36,6 @@ wing_table(std::integer_sequence<int, I...>) {
   return {{&csr_spmm_wing_kernel<I + 1, WING_U, WING_TPR>...}};
 }
 const auto kWing = wing_table(std::make_integer_sequence<int, WING_MAXS>{});
-__global__ void col_dot_partial_kernel(const double*, int64_t, const double*, int64_t, int,
-                                       double*);
-__global__ void col_dot_reduce_kernel(const double*, int, int, int, double*);
-__global__ void col_gs_update_kernel(double*, const double*, int64_t, const double*, int, int64_t,
-                                     int);
-__global__ void col_axpby_kernel(const double*, double*, const double*, const double*, int64_t,
-                                 int);
-__global__ void cg_xr_kernel(const double*, const double*, double*, double*, const double*,
-                             const double*, const int*, int64_t, int, int*);
-__global__ void cg_p_kernel(const double*, double*, const double*, const double*, const int*, int*,
-                            const double*, int, int*, int64_t, int);
-__global__ void cg_init_kernel(const double*, double, int, double*, int*, int*, int*);
-template <bool NT>
-__global__ void lz_dots_kernel(const double*, int64_t, int, int, const double*, const double*,
-                               int64_t, int, int, double*);
-__global__ void lz_scalar_kernel(const double*, int, int, int, double*, double*, double*, double*,
-                                 double*, int*, int*, double*, double*, int);
-template <int NR, bool NT>
-__global__ void lz_update_kernel(double*, int64_t, int, double*, const double*, const double*,
-                                 const double*, const double*, int);
-__global__ void rademacher_kernel(double*, int64_t, int, unsigned long long, int, double,
-                                  const int*);
-__global__ void csr_permute_kernel(const int64_t*, const int*, const double*, const int*,
-                                   const int*, int64_t, const int64_t*, int*, double*);
-__global__ void lz0_dot64_kernel(const double*, const double*, int64_t, int, double*);
-__global__ void lz0_alpha_kernel(const double*, const double*, int, int, int, int, double*, int*,
-                                 double*, double*, double*);
-__global__ void lz0_update_kernel(const double*, const double*, const double*, double*,
-                                  const double*, int64_t, int, double*);
-__global__ void lanczos_scalar_kernel(const double*, const double*, const double*, int, int, int,
-                                      int*, double*, double*, double*, double*, double*,
-                                      double*);
-void launch_ms_dots(const double* B, const double* R, int64_t n, int s, double* partial, int nblk,
-                    hipStream_t st, int sa);
-__global__ void rows_gather_kernel(const double*, int, const int*, int64_t, int, double*);
-__global__ void ms_init_kernel(MsScal, MsShift, const double*, int, int, int, int, MsPin*);
-__global__ void ms_cg2_update_kernel(const double*, double*, const double*, double*,
-                                     MsScal, MsScal, MsShift, const double*, double*,
-                                     const double*, int, int, int, double, int, int64_t, MsPin*);
-__global__ void ms_cg2_reduce_kernel(const double*, int, int, const double*, int, int, double*);
-__global__ void ms_cg2_close_kernel(MsScal, MsShift, const double*, int, int, int);
-__global__ void ms_compact_kernel(MsCompactArgs);
-__global__ void ms_dots2_kernel(const double*, const double*, int64_t, int, double*);
-template <int CT>
-__global__ void dense_mm_kernel(const double*, int64_t, int64_t, const double*, int, int, double*);
-__global__ void dense_mm_reduce_kernel(const double*, int, int64_t, const double*, double, double*);
 int op_view(const gpmi_op* op, OpView* v);            // gpmi_api.hip
 int matern_params_host(double nu, MaternParams* P);   // gpmi_api.hip
 int set_error(int code, const char* msg);             // gpmi_api.hip
@@ -144,7 +65,6 @@ namespace {
 
 constexpr int NBLK = 256;   // fixed reduction grid (deterministic sums)
 constexpr int MAXS = 32;    // vector-block width per device pass
-constexpr int MS_NBLK = 128; // row blocks of the multi-shift dot partials
 
 struct Guard {
   int prev = -1;
@@ -162,8 +82,6 @@ struct Guard {
 
 }  // namespace
 
-constexpr int MS_BATCH = 8;   // multi-shift CG iterations between host polls
-
 struct gpmi_sp {
   int device = 0;
   int64_t n = 0, nnz = 0;
@@ -178,7 +96,6 @@ struct gpmi_sp {
   double* partial = nullptr;   // [NBLK][J][s]
   size_t partial_doubles = 0;
   double* small = nullptr;     // coefficient / reduction arrays
-  double* msbuf = nullptr;     // multi-shift CG scalar state
   double* lz = nullptr;        // Lanczos scalars (lanczos_block)
   size_t lz_doubles = 0;
   double* lzd = nullptr;       // DCGS2 Lanczos scalars (lanczos_block_dcgs2)
@@ -188,24 +105,24 @@ struct gpmi_sp {
   // that it may run from another host thread beside a Lanczos on `stream` (the
   // sparse step's two independent halves overlap on the device)
   hipStream_t ms_stream = nullptr;
-  double* ms_ws = nullptr;
+  double* ms_ws = nullptr;                 // B [n][nb] and the host staging [n][nrhs]
   double* rhs_dev = nullptr;               // resident RHS block [n][rhs_nrhs] (gpmi_sp_set_rhs)
   int rhs_nrhs = 0;
   size_t ms_ws_doubles = 0;
-  double* ms_partial = nullptr;
-  size_t ms_partial_doubles = 0;
   void* ms_pin = nullptr;                  // pinned flags / r.r of two CG batches
-  double* cg2_buf = nullptr;               // the Chronopoulos-Gear form's dot rows
-  // its compacted state (active columns only): two, alternating, so that a second
-  // compaction gathers from the first one's buffer into the other
-  double* ms_cbuf[2] = {nullptr, nullptr};
-  size_t ms_cbuf_doubles[2] = {0, 0};
+  // the Chronopoulos-Gear form's dot rows (sized for the start width), the shifts and
+  // the two flags
+  double* cg2_buf = nullptr;
+  // the block's state (MsBlock: R, W, S, the B^T r partials, the scalars), two buffers,
+  // alternating: the start block in [0], compaction k (1-based) gathers the active
+  // columns from the current one into [k & 1]
+  double* ms_blk[2] = {nullptr, nullptr};
+  size_t ms_blk_doubles[2] = {0, 0};
   double* ms_gfin = nullptr;   // the stopped columns' final Grams [S nb][s0]
   size_t ms_gfin_doubles = 0;
   size_t cg2_doubles = 0;
   hipEvent_t ms_ev[2] = {nullptr, nullptr};
   std::mutex win_mu;           // the lazy X-window build (ensure_window)
-  size_t msbuf_doubles = 0;
   int last_converged = 1;      // last gpmi_sp_cg / gpmi_sp_msgram met rtol in every column
   int last_compactions = 0;    // active-column compactions of the last multi-shift CG
   // its launch segments: (block width, iterations launched at that width), in order
@@ -259,21 +176,15 @@ struct gpmi_sp {
 
 namespace {
 
-int ensure_ws(gpmi_sp* sp, size_t doubles) {
-  if (sp->ws_doubles >= doubles) return 0;
-  if (sp->ws) SP_TRY(hipFree(sp->ws));
-  sp->ws = nullptr;
-  SP_TRY(hipMalloc(&sp->ws, sizeof(double) * doubles));
-  sp->ws_doubles = doubles;
-  return 0;
-}
-
-int ensure_partial(gpmi_sp* sp, size_t doubles) {
-  if (sp->partial_doubles >= doubles) return 0;
-  if (sp->partial) SP_TRY(hipFree(sp->partial));
-  sp->partial = nullptr;
-  SP_TRY(hipMalloc(&sp->partial, sizeof(double) * doubles));
-  sp->partial_doubles = doubles;
+// A workspace grown on demand: at least `need` doubles behind *buf (*have of them
+// now; the contents do not survive a growth).
+int grow(double** buf, size_t* have, size_t need) {
+  if (*have >= need) return 0;
+  if (*buf) SP_TRY(hipFree(*buf));
+  *buf = nullptr;
+  *have = 0;
+  SP_TRY(hipMalloc(buf, sizeof(double) * need));
+  *have = need;
   return 0;
 }
 
@@ -298,8 +209,8 @@ int ensure_window(gpmi_sp* sp) {
 }
 
 int build_window(gpmi_sp* sp) {
-  const int64_t nblk = (sp->n + WIN_ROWS_HOST - 1) / WIN_ROWS_HOST;
-  SP_TRY(hipMalloc(&sp->win_cols, sizeof(int) * (size_t)nblk * WIN_MAXU_HOST));
+  const int64_t nblk = (sp->n + WIN_ROWS - 1) / WIN_ROWS;
+  SP_TRY(hipMalloc(&sp->win_cols, sizeof(int) * (size_t)nblk * WIN_MAXU));
   SP_TRY(hipMalloc(&sp->win_u, sizeof(int) * (size_t)nblk));
   SP_TRY(hipMalloc(&sp->win_lidx, sizeof(unsigned short) * (size_t)std::max<int64_t>(1, sp->nnz)));
   hipLaunchKernelGGL(spmm_window_build_kernel, dim3((unsigned)nblk), dim3(256), 0, sp->stream,
@@ -321,7 +232,7 @@ int build_window(gpmi_sp* sp) {
   int mm = 0;
   for (int64_t b = 0; b < nblk; ++b)
     if (hu[(size_t)b] > 0) {
-      const int64_t r0 = b * WIN_ROWS_HOST, r1 = std::min<int64_t>(r0 + WIN_ROWS_HOST, sp->n);
+      const int64_t r0 = b * WIN_ROWS, r1 = std::min<int64_t>(r0 + WIN_ROWS, sp->n);
       mm = std::max<int>(mm, (int)(hp[(size_t)r1] - hp[(size_t)r0]));
     }
   sp->win_maxm = mm;
@@ -333,10 +244,10 @@ int build_window(gpmi_sp* sp) {
       nz += v == 0;
     }
     fprintf(stderr, "[gpmi spmm] %lld blocks of %d rows: window mean %.1f max %d, %d unwindowed, "
-            "max block nnz %d\n", (long long)nblk, WIN_ROWS_HOST, su / (double)nblk, mu, nz, mm);
+            "max block nnz %d\n", (long long)nblk, WIN_ROWS, su / (double)nblk, mu, nz, mm);
   }
-  const size_t lds = (size_t)std::max(1, mu) * WIN_CS_HOST * 8 + 10 * (size_t)mm + 4 +
-                     4 * (WIN_ROWS_HOST + 1);
+  const size_t lds = (size_t)std::max(1, mu) * WIN_CS * 8 + 10 * (size_t)mm + 4 +
+                     4 * (WIN_ROWS + 1);
   // the windowed kernel pays off while several workgroups fit a CU (2D tapered
   // Matern: windows of ~160 columns, 24 KB, 6 per CU: 1.2x); with 3D windows
   // (~350 columns, 49 KB, 3 per CU) it is slower than gathering from X
@@ -377,7 +288,7 @@ int spmm_kind(gpmi_sp* sp, int s, int* kind) {
   if (wmode != 0 && !(genv && std::atoi(genv) == 0) && s >= 1 && s <= WING_MAXS &&
       sp->win_maxu.load(std::memory_order_acquire) > 0 &&
       sizeof(double) * (size_t)std::max(sp->win_maxu.load(std::memory_order_acquire),
-                                        WIN_ROWS_HOST) * s <= (size_t)WING_MAX_LDS) {
+                                        WIN_ROWS) * s <= (size_t)WING_MAX_LDS) {
     *kind = 5;
     return 0;
   }
@@ -422,7 +333,7 @@ int spmm_launch(gpmi_sp* sp, const double* X, double* Y, int s, double eta, hipS
     // [64][2s] rows of X . Y and X . X (the Chronopoulos-Gear multi-shift CG)
     const size_t lds = sizeof(double) * (size_t)s *
                        (size_t)std::max(sp->win_maxu.load(std::memory_order_acquire),
-                                        (dots2 ? 2 : 1) * WIN_ROWS_HOST);
+                                        (dots2 ? 2 : 1) * WIN_ROWS);
     auto kfn = kWing[s - 1];
     const int tpr = WING_TPR;
     hipLaunchKernelGGL(kfn, dim3((unsigned)sp->win_nblk), dim3(64 * tpr), lds, st, sp->indptr,
@@ -434,9 +345,9 @@ int spmm_launch(gpmi_sp* sp, const double* X, double* Y, int s, double eta, hipS
   }
   if (kind == 1) {
     // window + the largest windowed block's values, positions and row starts
-    const size_t lds = sizeof(double) * WIN_CS_HOST *
+    const size_t lds = sizeof(double) * WIN_CS *
                            (size_t)std::max(1, sp->win_maxu.load(std::memory_order_acquire)) +
-                       10 * (size_t)sp->win_maxm + 4 + sizeof(int) * (WIN_ROWS_HOST + 1);
+                       10 * (size_t)sp->win_maxm + 4 + sizeof(int) * (WIN_ROWS + 1);
     hipLaunchKernelGGL(csr_spmm_win_kernel,
                        dim3((unsigned)sp->win_nblk),
                        dim3(256), lds, st, sp->indptr, sp->indices, sp->win_lidx, sp->data,
@@ -509,7 +420,7 @@ int spmm(gpmi_sp* sp, const double* X, double* Y, int s, double eta, hipStream_t
 int col_dots(gpmi_sp* sp, const double* A, int64_t strideA, int J, const double* B, int s,
              double* out, double* partial = nullptr, hipStream_t st = nullptr) {
   if (!partial) {
-    int rc = ensure_partial(sp, (size_t)NBLK * J * s);
+    int rc = grow(&sp->partial, &sp->partial_doubles, (size_t)NBLK * J * s);
     if (rc) return rc;
     partial = sp->partial;
   }
@@ -550,12 +461,7 @@ int lanczos_block(gpmi_sp* sp, double* V, double* W, int s, int steps, double* h
   // alpha/beta tables [s][steps], two axpby coefficient pairs and the dead flags
   const size_t need = (size_t)2 * (steps + 1) * MAXS + MAXS + (size_t)2 * MAXS * steps +
                       4 * MAXS + MAXS;
-  if (sp->lz_doubles < need) {
-    if (sp->lz) SP_TRY(hipFree(sp->lz));
-    sp->lz = nullptr;
-    SP_TRY(hipMalloc(&sp->lz, sizeof(double) * need));
-    sp->lz_doubles = need;
-  }
+  if (int rc = grow(&sp->lz, &sp->lz_doubles, need)) return rc;
   double* H1 = sp->lz;
   double* H2 = H1 + (size_t)(steps + 1) * MAXS;
   double* nrm = H2 + (size_t)(steps + 1) * MAXS;
@@ -621,18 +527,13 @@ int lanczos_block_plain(gpmi_sp* sp, double* U, double* Y, int s, int steps, dou
   const int64_t n = sp->n, ns = n * s;
   const int nb = (int)((n + 63) / 64);
   const size_t need = 5 * (size_t)s + 2 * (size_t)s * steps + s;
-  if (sp->lz_doubles < need) {
-    if (sp->lz) SP_TRY(hipFree(sp->lz));
-    sp->lz = nullptr;
-    SP_TRY(hipMalloc(&sp->lz, sizeof(double) * need));
-    sp->lz_doubles = need;
-  }
+  if (int rc = grow(&sp->lz, &sp->lz_doubles, need)) return rc;
   double* st = sp->lz;
   double* coef = st + 2 * s;
   double* dal = coef + 3 * s;
   double* dbe = dal + (size_t)s * steps;
   int* dead = reinterpret_cast<int*>(dbe + (size_t)s * steps);
-  int rc = ensure_partial(sp, (size_t)nb * 3 * s);
+  int rc = grow(&sp->partial, &sp->partial_doubles, (size_t)nb * 3 * s);
   if (rc) return rc;
   double* pq = sp->partial;                 // [s][nb]: u_k . y
   double* pv = pq + (size_t)nb * s;         // [2][s][nb]: ||u_{k+1}||^2, u_{k+1} . u_k
@@ -683,12 +584,7 @@ int lanczos_block_dcgs2(gpmi_sp* sp, double* V, double* U, double* Y, int s, int
   const size_t hsz = (size_t)(steps + 2) * (steps + 1);
   const size_t need = (size_t)s * hsz + (size_t)(2 * steps + 2) * s + (size_t)steps * s +
                       (size_t)(steps + 1) * s + 2 * (size_t)s + 2 * (size_t)s * steps + 2 * s;
-  if (sp->lzd_doubles < need) {
-    if (sp->lzd) SP_TRY(hipFree(sp->lzd));
-    sp->lzd = nullptr;
-    SP_TRY(hipMalloc(&sp->lzd, sizeof(double) * need));
-    sp->lzd_doubles = need;
-  }
+  if (int rc = grow(&sp->lzd, &sp->lzd_doubles, need)) return rc;
   double* H = sp->lzd;
   double* d = H + (size_t)s * hsz;
   double* cv = d + (size_t)(2 * steps + 2) * s;
@@ -702,7 +598,7 @@ int lanczos_block_dcgs2(gpmi_sp* sp, double* V, double* U, double* Y, int s, int
   // row blocks of the dot partials (fixed: deterministic; 256 / 1024 / 2048 measured
   // 2-5 % slower at cfg 5)
   const int lz_nb = LZ_NB;
-  int rc = ensure_partial(sp, (size_t)lz_nb * (2 * steps + 2) * s);
+  int rc = grow(&sp->partial, &sp->partial_doubles, (size_t)lz_nb * (2 * steps + 2) * s);
   if (rc) return rc;
   SP_TRY(hipMemsetAsync(H, 0, sizeof(double) * s * hsz, sp->stream));
   SP_TRY(hipMemsetAsync(dal, 0, sizeof(double) * 2 * s * steps, sp->stream));
@@ -1038,15 +934,13 @@ int gpmi_sp_destroy(gpmi_sp* sp) {
   if (sp->ws) (void)hipFree(sp->ws);
   if (sp->partial) (void)hipFree(sp->partial);
   if (sp->small) (void)hipFree(sp->small);
-  if (sp->msbuf) (void)hipFree(sp->msbuf);
   if (sp->lz) (void)hipFree(sp->lz);
   if (sp->lzd) (void)hipFree(sp->lzd);
   if (sp->ms_ws) (void)hipFree(sp->ms_ws);
   if (sp->rhs_dev) (void)hipFree(sp->rhs_dev);
-  if (sp->ms_partial) (void)hipFree(sp->ms_partial);
   if (sp->ms_pin) (void)hipHostFree(sp->ms_pin);
   if (sp->cg2_buf) (void)hipFree(sp->cg2_buf);
-  for (double* cb : sp->ms_cbuf)
+  for (double* cb : sp->ms_blk)
     if (cb) (void)hipFree(cb);
   if (sp->ms_gfin) (void)hipFree(sp->ms_gfin);
   for (hipEvent_t e : sp->ev_pool) (void)hipEventDestroy(e);
@@ -1160,7 +1054,7 @@ int gpmi_sp_spmm(gpmi_sp* sp, double eta, const double* X, int64_t ld, int ncol,
   const int64_t n = sp->n;
   for (int c0 = 0; c0 < ncol; c0 += MAXS) {
     const int s = std::min(MAXS, ncol - c0);
-    int rc = ensure_ws(sp, (size_t)2 * n * s);
+    int rc = grow(&sp->ws, &sp->ws_doubles, (size_t)2 * n * s);
     if (rc) return rc;
     std::vector<double> h((size_t)n * s);
     for (int64_t i = 0; i < n; ++i)
@@ -1193,7 +1087,7 @@ int gpmi_sp_lanczos_ex(gpmi_sp* sp, int nprobe, int steps, uint64_t seed, int pr
   for (int p0 = 0; p0 < nprobe; p0 += MAXS) {
     const int s = std::min(MAXS, nprobe - p0);
     // the basis and a work block (the plain recurrence: three rotating blocks + one)
-    int rc = ensure_ws(sp, (size_t)std::max(steps + 2, 4) * n * s);
+    int rc = grow(&sp->ws, &sp->ws_doubles, (size_t)std::max(steps + 2, 4) * n * s);
     if (rc) return rc;
     double* V = sp->ws;
     double* W = sp->ws + (size_t)(steps + 1) * n * s;
@@ -1254,7 +1148,7 @@ int gpmi_sp_cg(gpmi_sp* sp, double eta, const double* rhs, int64_t ld, int nrhs,
   for (int c0 = 0; c0 < nrhs; c0 += MAXS) {
     const int s = std::min(MAXS, nrhs - c0);
     const int64_t ns = n * s;
-    int rc = ensure_ws(sp, (size_t)4 * ns);
+    int rc = grow(&sp->ws, &sp->ws_doubles, (size_t)4 * ns);
     if (rc) return rc;
     double* X = sp->ws;
     double* Rr = X + ns;
@@ -1349,288 +1243,145 @@ int gpmi_sp_cg(gpmi_sp* sp, double eta, const double* rhs, int64_t ld, int nrhs,
 // (A two-launch form that summed the rows inside the SpMM and the update by group
 // last-arriver tickets was slower: every block then drains its stores before its
 // ticket, 12.6 -> 25 us per cfg 4 SpMM.)
-static int msgram_cg2(gpmi_sp* sp, const double* etas, int neta, const double* rhs,
-                      int64_t ld, int nrhs, int c_lo, int c_hi, double rtol, int maxiter,
-                      double* G, int* iterations) {
-  const int nsub = c_hi - c_lo;
-  const bool full = nsub == nrhs;
-  Guard g(sp->device);
-  const int64_t n = sp->n;
-  const int S = neta;
-  int s = nsub;
-  int kind = 0;
-  {
-    int rc0 = spmm_kind(sp, s, &kind);
-    if (rc0) return rc0;
-    // Padding (the Gram of the real columns is unchanged by a zero column, inactive
-    // from the start: ||b|| = 0): the window SpMM at s = 11 stages 12-column rows with
-    // 16-byte loads: cfg 5 s = 11 88 -> 73 us per launch (round 3)
-    if (full && kind == 5 && s == 11 && S * (s + 1) <= 1024) ++s;
-    if ((rc0 = spmm_kind(sp, s, &kind))) return rc0;
-  }
-  const int nbd = full ? s : nrhs;
-  const int64_t nsb = n * nbd;
-  if (!sp->ms_stream) {
-    // the CG's own stream, at the same (normal) dispatch priority as the Lanczos's.
-    // Round 5 gave it the high priority (cfg 5 11.85 -> 11.46 ms, when the CG alone took
-    // 8.8 ms); since the compaction the CG alone takes 6.4 ms and a starved Lanczos (4.1
-    // ms alone) plus its host-side quadrature became the step's tail: round 6 alternating
-    // runs, high / normal / low: cfg 5 9.80-9.92 / 9.40-9.44 / 9.77-10.05 ms, cfg 4
-    // 2.86-2.90 / 2.80-2.82 / 2.83-2.86 ms.
-    SP_TRY(hipStreamCreateWithFlags(&sp->ms_stream, hipStreamNonBlocking));
-  }
-  int64_t ns = n * s;
-  const int s0 = s;   // the block's width at the start (compaction narrows s)
-  const double eta0 = *std::min_element(etas, etas + neta);
-  int rc = 0;
+//
+// Three phases (msgram_cg2): setup (ms_alloc, ms_start), the iterations (ms_schedule of
+// gpmi_ms_sched.h decides the batches, the slot reads and the compactions; MsDev below
+// only queues what it is told to), and the read-back (ms_finish).
+
+// One block of the multi-shift CG, s columns wide: the vectors, the update's B^T r
+// block partials [nbd s][MS_UB] and the scalar state.
+struct MsBlock {
+  double *R, *W, *S, *bpart;
+  MsScal sc[2];   // by iteration parity
+  MsShift sh;     // (flags and it_stop belong to the run: every block's point to the same)
+  int s;
+};
+
+// The one layout of a block: carves *b (all but sh.flags and sh.it_stop) out of base and
+// returns the doubles it takes; base == nullptr: the size only. R, W and S start on 16
+// bytes (the window SpMM loads their rows 16 bytes at a time).
+static size_t ms_carve(double* base, int64_t n, int s, int nbd, int S, MsBlock* b) {
+  size_t off = 0;
+  auto take = [&](size_t d) {
+    double* p = base ? base + off : nullptr;
+    off += d;
+    return p;
+  };
   auto even = [](size_t d) { return (d + 1) & ~(size_t)1; };
-  // B [n][nbd], the host staging [n][nrhs], and R, W, S [n][s] (16-byte aligned)
-  const size_t wsn = even((size_t)nsb) + even((size_t)n * nrhs) + 3 * even((size_t)ns);
-  if (sp->ms_ws_doubles < wsn) {
-    if (sp->ms_ws) SP_TRY(hipFree(sp->ms_ws));
-    sp->ms_ws = nullptr;
-    SP_TRY(hipMalloc(&sp->ms_ws, sizeof(double) * wsn));
-    sp->ms_ws_doubles = wsn;
+  MsBlock k{};
+  k.s = s;
+  k.R = take(even((size_t)n * s));
+  k.W = take(even((size_t)n * s));
+  k.S = take(even((size_t)n * s));
+  k.bpart = take((size_t)MS_UB * nbd * s);
+  for (MsScal& c : k.sc) {
+    c.rr = take(s);
+    c.a = take(s);
+    c.a_prev = take(s);
+    c.beta = take(s);
+    c.active = reinterpret_cast<int*>(take(s));
   }
-  double* Bd = sp->ms_ws;
-  double* Hs = Bd + even((size_t)nsb);
-  double* Rd = Hs + even((size_t)n * nrhs);
-  double* Wd = Rd + even((size_t)ns);
-  double* Sd = Wd + even((size_t)ns);
-  // dot rows: the SpMM's per-block [nblk][2s]; the update's B^T r per-block
-  // [MS_UB][nbd s]; their sums [2s + nbd s] (ms_cg2_reduce_kernel); the init partials
-  // [MS_NBLK][ne]
-  const int64_t nblk_sp = kind == 5 ? sp->win_nblk : MS_DOT_BLK;
-  int neb = nbd * s;
-  const int ne0 = nbd * s + s;
-  const size_t c_sp = (size_t)nblk_sp * 2 * s, c_bp = (size_t)MS_UB * neb;
-  const size_t c_red = 2 * (size_t)s + neb, c_init = (size_t)MS_NBLK * ne0;
-  const size_t need = c_sp + c_bp + c_red + c_init;
-  if (sp->cg2_doubles < need) {
-    if (sp->cg2_buf) SP_TRY(hipFree(sp->cg2_buf));
-    sp->cg2_buf = nullptr;
-    SP_TRY(hipMalloc(&sp->cg2_buf, sizeof(double) * need));
-    sp->cg2_doubles = need;
+  k.sh.bn2 = take(s);
+  k.sh.z = take((size_t)S * s);
+  k.sh.z_prev = take((size_t)S * s);
+  k.sh.bp = take((size_t)S * nbd * s);
+  k.sh.g = take((size_t)S * nbd * s);
+  if (base) {
+    k.sh.flags = b->sh.flags;
+    k.sh.it_stop = b->sh.it_stop;
+    *b = k;
   }
-  double* spart = sp->cg2_buf;
-  double* bpart = spart + c_sp;
-  double* dred = bpart + c_bp;
-  double* ipart = dred + c_red;
-  // scalar state: MsScal x 2 (parity), MsShift
-  const size_t sneed = 2 * (4 * (size_t)s + s) + (size_t)s + 2 * (size_t)S * s +
-                       2 * (size_t)S * nbd * s + S + 4;
-  if (sp->msbuf_doubles < sneed) {
-    if (sp->msbuf) SP_TRY(hipFree(sp->msbuf));
-    sp->msbuf = nullptr;
-    SP_TRY(hipMalloc(&sp->msbuf, sizeof(double) * sneed));
-    sp->msbuf_doubles = sneed;
+  return off;
+}
+
+// The device side of the iterations (the Dev of ms_schedule): the current block, one
+// iteration's launches, the two slots' events, and the compaction's gather.
+struct MsDev {
+  gpmi_sp* sp;
+  hipStream_t str;
+  int64_t n;
+  int S, nbd, s0;         // shifts, columns of B, the block's width at the start
+  double eta0, rtol;
+  double *Bd, *Hs;        // B [n][nbd], the host staging [n][nrhs]
+  // dot rows: the SpMM's per-block [nblk][2s]; their sums and the B^T r sums [2s + nbd s]
+  // (ms_cg2_reduce_kernel); the init partials [MS_NBLK][ne]
+  double *spart, *dred, *ipart;
+  double* dshift;         // [S] eta_j - eta_0
+  MsPin *pin_host, *pin_dev;
+  MsBlock blk;            // the current block, carved out of sp->ms_blk[buf]
+  int buf;
+
+  MsPin* pin() { return pin_host; }
+  int mark(int slot) {
+    SP_TRY(hipEventRecord(sp->ms_ev[slot], str));
+    return 0;
   }
-  double* q = sp->msbuf;
-  MsScal sc[2];
-  for (int b = 0; b < 2; ++b) {
-    sc[b].rr = q; q += s;
-    sc[b].a = q; q += s;
-    sc[b].a_prev = q; q += s;
-    sc[b].beta = q; q += s;
-    sc[b].active = reinterpret_cast<int*>(q); q += s;
+  int wait(int slot) {
+    SP_TRY(hipEventSynchronize(sp->ms_ev[slot]));
+    return 0;
   }
-  MsShift sh;
-  sh.bn2 = q; q += s;
-  sh.z = q; q += (size_t)S * s;
-  sh.z_prev = q; q += (size_t)S * s;
-  sh.bp = q; q += (size_t)S * nbd * s;
-  sh.g = q; q += (size_t)S * nbd * s;
-  double* dshift = q; q += S;
-  sh.flags = reinterpret_cast<int*>(q); q += 1;
-  sh.it_stop = reinterpret_cast<int*>(q); q += 1;
-  sp->last_converged = 0;
-  hipStream_t str = sp->ms_stream;
-  {
-    const double* Hsrc = Hs;
-    if (!rhs) {
-      Hsrc = sp->rhs_dev;
-    } else if (ld == nrhs) {
-      SP_TRY(hipMemcpyAsync(Hs, rhs, sizeof(double) * n * nrhs, hipMemcpyHostToDevice, str));
-    } else {
-      std::vector<double> h((size_t)n * nrhs);
-      for (int64_t i = 0; i < n; ++i)
-        for (int c = 0; c < nrhs; ++c) h[(size_t)i * nrhs + c] = rhs[i * ld + c];
-      SP_TRY(hipMemcpyAsync(Hs, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, str));
-      SP_TRY(hipStreamSynchronize(str));
-    }
-    hipLaunchKernelGGL(rows_gather_kernel, dim3(grid_ns(n, nbd)), dim3(256), 0, str, Hsrc, nrhs,
-                       (const int*)sp->perm_d, n, nbd, Bd);
-    SP_LAUNCH("rows_gather_kernel");
-    std::vector<double> hd(S);
-    for (int j = 0; j < S; ++j) hd[j] = etas[j] - eta0;
-    SP_TRY(hipMemcpyAsync(dshift, hd.data(), sizeof(double) * S, hipMemcpyHostToDevice, str));
-    if (full) {
-      SP_TRY(hipMemcpyAsync(Rd, Bd, sizeof(double) * ns, hipMemcpyDeviceToDevice, str));
-    } else {
-      hipLaunchKernelGGL(rows_gather_kernel, dim3(grid_ns(n, s)), dim3(256), 0, str, Bd + c_lo,
-                         nbd, (const int*)nullptr, n, s, Rd);
-      SP_LAUNCH("rows_gather_kernel");
-    }
-    // s_{-1} = 0 (beta_{-1} = 0 multiplies it: no NaN may stand there)
-    SP_TRY(hipMemsetAsync(Sd, 0, sizeof(double) * ns, str));
-  }
-  launch_ms_dots(Bd, Rd, n, s, ipart, MS_NBLK, str, nbd);
-  SP_LAUNCH("ms_dots_partial_kernel");
-  if (!sp->ms_pin) {
-    // coherent: the batch's last update kernel stores the end state into it directly
-    SP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sp->ms_pin), 2 * sizeof(MsPin),
-                         hipHostMallocCoherent | hipHostMallocMapped));
-    for (hipEvent_t* e : {&sp->ms_ev[0], &sp->ms_ev[1]})
-      SP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
-  }
-  MsPin* pin = reinterpret_cast<MsPin*>(sp->ms_pin);
-  MsPin* pin_dev = nullptr;
-  SP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&pin_dev), sp->ms_pin, 0));
-  hipLaunchKernelGGL(ms_init_kernel, dim3(1), dim3(1024), 0, str, sc[0], sh, ipart, MS_NBLK, S, s,
-                     nbd, pin_dev);
-  SP_LAUNCH("ms_init_kernel");
-  int it = 0;
-  // one iteration's launches on str (parity it & 1 picks the scalar and B^T r buffers)
-  auto iterate = [&](int k, MsPin* pin_out) -> int {
+
+  // one iteration's launches on str (parity k & 1 picks the scalar buffers)
+  int iterate(int k, int slot) {
+    const int s = blk.s, neb = nbd * s;
     int rows = 0;
-    int rc1 = spmm(sp, Rd, Wd, s, eta0, str, spart, &rows, 1);
-    if (rc1) return rc1;
+    if (int rc = spmm(sp, blk.R, blk.W, s, eta0, str, spart, &rows, 1)) return rc;
     if (rows == 0) {
-      hipLaunchKernelGGL(ms_dots2_kernel, dim3(MS_DOT_BLK), dim3(256), 0, str, (const double*)Rd,
-                         (const double*)Wd, n, s, spart);
+      hipLaunchKernelGGL(ms_dots2_kernel, dim3(MS_DOT_BLK), dim3(256), 0, str,
+                         (const double*)blk.R, (const double*)blk.W, n, s, spart);
       SP_LAUNCH("ms_dots2_kernel");
       rows = MS_DOT_BLK;
     }
     hipLaunchKernelGGL(ms_cg2_reduce_kernel, dim3(2 * s + neb), dim3(256), 0, str,
-                       (const double*)spart, rows, s, (const double*)bpart, MS_UB, neb, dred);
+                       (const double*)spart, rows, s, (const double*)blk.bpart, MS_UB, neb, dred);
     SP_LAUNCH("ms_cg2_reduce_kernel");
     hipLaunchKernelGGL(ms_cg2_update_kernel, dim3(MS_UB + 1), dim3(256), 0, str,
-                       (const double*)Bd, Rd, (const double*)Wd, Sd, sc[k & 1],
-                       sc[(k + 1) & 1], sh, (const double*)dred, bpart, (const double*)dshift, S,
-                       s, nbd, rtol * rtol, k, n, pin_out);
+                       (const double*)Bd, blk.R, (const double*)blk.W, blk.S, blk.sc[k & 1],
+                       blk.sc[(k + 1) & 1], blk.sh, (const double*)dred, blk.bpart,
+                       (const double*)dshift, S, s, nbd, rtol * rtol, k, n,
+                       slot >= 0 ? pin_dev + slot : (MsPin*)nullptr);
     SP_LAUNCH("ms_cg2_update_kernel");
     return 0;
-  };
-  std::vector<int> hact(s);
-  // Iterations run in batches between host reads of the stop flags. Each batch's last
-  // update kernel writes its end state (active flags, the negative-curvature flag,
-  // gamma) into host-mapped pinned memory, read while the NEXT batch is already
-  // queued, so the device does not wait for the host between batches. The next
-  // batch's size comes from the residuals' decay: the iterations the slowest active
-  // column still needs at its rate since the previous read, beyond what is queued (at
-  // most MS_BATCH); when the queued iterations should suffice the host waits for them
-  // instead. Iterations past a column's stop leave it unchanged (zero steps).
-  int slot_it[2] = {0, 0};
-  std::vector<double> rr_seen(s, -1.0);
-  int it_seen = 0;
-  bool prev = false;
-  int nb = MS_BATCH;
-  int kb = 0;
-  // Active-column compaction (round 6). The block iterates until its slowest column
-  // converges, and a stopped column still costs its share of every SpMM and vector
-  // pass (zero steps). BASELINE cfg 5: the ten basis columns of [X z] stop at ~42
-  // iterations, the data column z runs to ~90. Once at most half of the columns are
-  // still active, their state (r, s, the scalars, the shift recurrences, the B^T r
-  // block partials) is gathered into a block of their width and the loop goes on
-  // there; the dropped columns' Grams are final and kept in ms_gfin. Every column's
-  // arithmetic is unchanged (the SpMM, the dots and the updates are per column): the
-  // Grams are bit-identical to the uncompacted block (test_msgram_compaction_*).
-  // GPMI_MS_COMPACT=0: off.
-  const char* cenv = std::getenv("GPMI_MS_COMPACT");
-  const bool compact_on = !(cenv && std::atoi(cenv) == 0);
-  // GPMI_MS_TRACE=1: each batch's size and each read's prediction on stderr (diagnostic)
-  const bool trace = std::getenv("GPMI_MS_TRACE") != nullptr;
-  std::vector<int> orig(s);   // each current column's index in the original block
-  for (int c = 0; c < s; ++c) orig[c] = c;
-  // the dropped columns' final Grams, on the device until the end
-  if (compact_on && s0 > 1) {
-    const size_t gneed = (size_t)S * nbd * s0;
-    if (sp->ms_gfin_doubles < gneed) {
-      if (sp->ms_gfin) SP_TRY(hipFree(sp->ms_gfin));
-      sp->ms_gfin = nullptr;
-      SP_TRY(hipMalloc(&sp->ms_gfin, sizeof(double) * gneed));
-      sp->ms_gfin_doubles = gneed;
-    }
   }
-  int compactions = 0;
-  int seg_start = 0;   // the iteration the current block width began at
-  std::vector<std::pair<int, int>> segments;
-  // narrow the block once at most half of its columns still iterate (one column left
-  // always qualifies; waiting for three quarters measured the same at cfg 4 and 5)
-  auto keep_target = [&]() { return std::max(1, s / 2); };
-  // The compaction, asynchronous (round 6): the kept columns are those active in the
-  // pinned slot rd the host has just read (a column that stopped since idles in the new
-  // block until the next compaction or the end). One launch on the CG's stream gathers
-  // the state into the other compaction buffer and scatters the dropped columns' final
-  // Grams into gfin; the host only switches its pointers. The slot rd was written by the
-  // last batch or the one before it; the gathers are queued behind every iteration, so
-  // they see the state at iteration `it` whichever it was.
-  auto compact = [&](int rd) -> int {
-    int map[MS_MAXS], drop[MS_MAXS];
-    int a = 0, nd = 0;
-    for (int c = 0; c < s; ++c) {
-      if (pin[rd].act[c]) map[a++] = c;
-      else drop[nd++] = c;
-    }
-    if (a == 0 || a > keep_target() || nd == 0) return 0;
-    const size_t na = even((size_t)n * a);
-    const size_t cneed = 3 * na + (size_t)MS_UB * nbd * a + 2 * 5 * (size_t)a + (size_t)a +
-                         4 * (size_t)S * nbd * a + 2;
-    const int cb = compactions & 1;   // (the current block may live in the other one)
-    if (sp->ms_cbuf_doubles[cb] < cneed) {
-      if (sp->ms_cbuf[cb]) SP_TRY(hipFree(sp->ms_cbuf[cb]));
-      sp->ms_cbuf[cb] = nullptr;
-      SP_TRY(hipMalloc(&sp->ms_cbuf[cb], sizeof(double) * cneed));
-      sp->ms_cbuf_doubles[cb] = cneed;
-    }
-    double* cq = sp->ms_cbuf[cb];
-    // the compacted block lives in ms_cbuf; the old block's buffers are left alone
-    double* Rn = cq; cq += na;
-    double* Wn = cq; cq += na;
-    double* Sn = cq; cq += na;
-    double* bpn = cq; cq += (size_t)MS_UB * nbd * a;
-    MsScal scn[2];
-    for (int b = 0; b < 2; ++b) {
-      scn[b].rr = cq; cq += a;
-      scn[b].a = cq; cq += a;
-      scn[b].a_prev = cq; cq += a;
-      scn[b].beta = cq; cq += a;
-      scn[b].active = reinterpret_cast<int*>(cq); cq += a;
-    }
-    MsShift shn = sh;   // flags, it_stop shared
-    shn.bn2 = cq; cq += a;
-    shn.z = cq; cq += (size_t)S * a;
-    shn.z_prev = cq; cq += (size_t)S * a;
-    shn.bp = cq; cq += (size_t)S * nbd * a;
-    shn.g = cq; cq += (size_t)S * nbd * a;
-    const MsScal& cur = sc[it & 1];
-    MsScal& ncur = scn[it & 1];
+
+  // One launch on the CG's stream gathers the kept columns' state (r, s, the scalars of
+  // parity it & 1, the shift recurrences, the B^T r block partials) into a block of
+  // width a and scatters the dropped columns' final Grams into ms_gfin; the host only
+  // switches its block. The new block is carved out of the buffer the current one is
+  // NOT in (the start block took ms_blk[0], compaction k takes ms_blk[k & 1]): the
+  // gather never writes the buffer it reads.
+  int compact(const int* map, int a, const int* drop, const int* drop_orig, int nd, int it) {
+    const int nbuf = buf ^ 1;
+    if (int rc = grow(&sp->ms_blk[nbuf], &sp->ms_blk_doubles[nbuf],
+                      ms_carve(nullptr, n, a, nbd, S, nullptr)))
+      return rc;
+    MsBlock nw = blk;   // (the run's flags and it_stop)
+    ms_carve(sp->ms_blk[nbuf], n, a, nbd, S, &nw);
+    const MsScal &cur = blk.sc[it & 1], &ncur = nw.sc[it & 1];
     MsCompactArgs A{};
     auto job = [&](const double* src, int64_t rows, int L, double* dst) {
       A.job[A.njob++] = MsCompactJob{src, dst, rows, L, 0};
     };
-    job(Rd, n, 1, Rn);
-    job(Sd, n, 1, Sn);
-    job(bpart, nbd, MS_UB, bpn);   // [cp s + c][vb] -> [cp a + c'][vb]
+    job(blk.R, n, 1, nw.R);
+    job(blk.S, n, 1, nw.S);
+    job(blk.bpart, nbd, MS_UB, nw.bpart);   // [cp s + c][vb] -> [cp a + c'][vb]
     job(cur.rr, 1, 1, ncur.rr);
     job(cur.a, 1, 1, ncur.a);
     job(cur.a_prev, 1, 1, ncur.a_prev);
     job(cur.beta, 1, 1, ncur.beta);
-    job(sh.bn2, 1, 1, shn.bn2);
-    job(sh.z, S, 1, shn.z);
-    job(sh.z_prev, S, 1, shn.z_prev);
-    job(sh.bp, (int64_t)S * nbd, 1, shn.bp);
-    job(sh.g, (int64_t)S * nbd, 1, shn.g);
-    A.s = s;
+    job(blk.sh.bn2, 1, 1, nw.sh.bn2);
+    job(blk.sh.z, S, 1, nw.sh.z);
+    job(blk.sh.z_prev, S, 1, nw.sh.z_prev);
+    job(blk.sh.bp, (int64_t)S * nbd, 1, nw.sh.bp);
+    job(blk.sh.g, (int64_t)S * nbd, 1, nw.sh.g);
+    A.s = blk.s;
     A.a = a;
     A.nd = nd;
     A.s0 = s0;
-    for (int q = 0; q < a; ++q) A.map[q] = map[q];
-    for (int d = 0; d < nd; ++d) {
-      A.drop[d] = drop[d];
-      A.drop_orig[d] = orig[drop[d]];
-    }
-    A.g = sh.g;
+    std::copy(map, map + a, A.map);
+    std::copy(drop, drop + nd, A.drop);
+    std::copy(drop_orig, drop_orig + nd, A.drop_orig);
+    A.g = blk.sh.g;
     A.gfin = sp->ms_gfin;
     A.SN = (int64_t)S * nbd;
     A.act_src = cur.active;
@@ -1641,170 +1392,134 @@ static int msgram_cg2(gpmi_sp* sp, const double* etas, int neta, const double* r
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(1024, (most + 255) / 256));
     hipLaunchKernelGGL(ms_compact_kernel, dim3(gx, A.njob + 1), dim3(256), 0, str, A);
     SP_LAUNCH("ms_compact_kernel");
-    // host-side state in the new column order (pin's bn2 is written once, at the start;
-    // a batch still in flight writes its old-order end state into the slot after rd's,
-    // which is rewritten by the next batch before it is read)
-    std::vector<int> norig(a);
-    std::vector<double> nrr(a);
-    for (int q = 0; q < a; ++q) {
-      norig[q] = orig[map[q]];
-      nrr[q] = rr_seen[map[q]];
-    }
-    for (int qs = 0; qs < 2; ++qs) {
-      double bn[MS_MAXS];
-      for (int q = 0; q < a; ++q) bn[q] = pin[qs].bn2[map[q]];
-      for (int q = 0; q < a; ++q) pin[qs].bn2[q] = bn[q];
-    }
-    orig.swap(norig);
-    rr_seen.swap(nrr);
-    segments.emplace_back(s, it - seg_start);
-    seg_start = it;
-    Rd = Rn;
-    Wd = Wn;
-    Sd = Sn;
-    bpart = bpn;
-    sc[0] = scn[0];
-    sc[1] = scn[1];
-    sh = shn;
-    s = a;
-    ns = n * s;
-    neb = nbd * s;
-    hact.assign(s, 0);
-    prev = false;
-    ++compactions;
+    blk = nw;
+    buf = nbuf;
     return 0;
-  };
-  // Predictions from each read (round 6): need_after, the iterations the slowest active
-  // column still needs beyond those queued (it; unknown at first: a batch at a time), and
-  // compact_at, the iteration by which at most half of the block's columns should still
-  // iterate (each column's stop from its own rate; -1: none predicted). A batch sized to
-  // end where the prediction says the CG stops, or where the block can be compacted, is
-  // read as soon as it ends instead of after the next batch is queued: before, the
-  // iterations queued past the stop ran at full cost (cfg 4: 111 launched for 102) and
-  // the compaction waited a batch at the full width.
-  int need_after = maxiter;
-  int compact_at = -1;
-  int forced_reads = 0;   // compaction reads that found too few columns stopped
-  std::vector<double> stops;
-  auto read_slot = [&](int qs) -> int {
-    SP_TRY(hipEventSynchronize(sp->ms_ev[qs]));
-    if (pin[qs].flag) {
-      SP_TRY(hipStreamSynchronize(str));
-      return set_error(1, "multi-shift CG: p^T (K + min(eta) I) p <= 0 (not positive definite)");
-    }
-    bool any = false;
-    double needm = 0.0;
-    const int at = slot_it[qs];
-    int nact = 0;
-    stops.clear();
-    for (int c = 0; c < s; ++c) {
-      if (!pin[qs].act[c]) continue;
-      any = true;
-      ++nact;
-      // (at the first read the rate is from r_0 = b: ||r_0||^2 = ||b||^2, so the first
-      // batches need no wait for a second read)
-      const double r1 = pin[qs].rr[c], target = rtol * rtol * pin[qs].bn2[c];
-      const double r0 = rr_seen[c] < 0.0 && it_seen == 0 ? pin[qs].bn2[c] : rr_seen[c];
-      double m = (double)MS_BATCH;
-      bool rated = false;
-      if (r0 > 0.0 && r1 > 0.0 && r1 < r0 && at > it_seen && target > 0.0) {
-        m = std::log(target / r1) / (std::log(r1 / r0) / (double)(at - it_seen));
-        rated = true;
-      }
-      needm = std::max(needm, m);
-      stops.push_back(rated ? (double)at + std::max(0.0, m) : 1e300);
-      rr_seen[c] = r1;
-    }
-    it_seen = at;
-    // clamped before the conversion: a stagnating residual (r1 / r0 -> 1) gives a huge m
-    const double rem = std::min((double)maxiter, std::ceil((double)at + needm)) - (double)it;
-    need_after = (int)std::max(-1.0, rem);
-    compact_at = -1;
-    const int k = nact - keep_target();   // columns that must stop before the block narrows
-    if (compact_on && s > 1 && any && k >= 1 && forced_reads < 2) {
-      std::nth_element(stops.begin(), stops.begin() + (k - 1), stops.end());
-      const double tk = stops[k - 1];
-      if (tk < (double)maxiter) compact_at = (int)std::ceil(tk);
-    }
-    if (trace)
-      std::fprintf(stderr,
-                   "[ms] read slot at %d (queued %d, width %d, active %d): need %.1f more, "
-                   "after %d, compact at %d%s\n",
-                   at, it, s, nact, needm, need_after, compact_at, any ? "" : " (all stopped)");
-    return any ? 0 : 2;
-  };
-  while (it < maxiter) {
-    nb = std::max(1, std::min(nb, maxiter - it));
-    const int qs = kb & 1;
-    for (int i = 0; i < nb; ++i, ++it)
-      if ((rc = iterate(it, i + 1 == nb ? pin_dev + qs : nullptr))) return rc;
-    SP_TRY(hipEventRecord(sp->ms_ev[qs], str));
-    slot_it[qs] = it;
-    ++kb;
-    need_after -= nb;
-    int read = -1;   // the slot read this round (its flags drive the compaction)
-    if (prev) {
-      const int r = read_slot(qs ^ 1);
-      if (r == 2) break;
-      if (r) return r;
-      read = qs ^ 1;
-    }
-    prev = true;
-    auto compactable = [&](int q) {
-      int nact = 0;
-      for (int c = 0; c < s; ++c) nact += pin[q].act[c] ? 1 : 0;
-      return nact <= keep_target();
-    };
-    const bool can_compact = compact_on && s > 1 && it < maxiter;
-    // the stop, or the compaction, predicted within the iterations queued: read them now
-    const bool due = can_compact && compact_at >= 0 && compact_at <= it &&
-                     !(read >= 0 && compactable(read));
-    if (need_after <= 0 || due) {
-      const int r = read_slot(qs);
-      if (r == 2) break;
-      if (r) return r;
-      prev = false;
-      read = qs;
-      if (due && !compactable(qs)) ++forced_reads;
-    }
-    if (can_compact && read >= 0 && compactable(read)) {
-      if ((rc = compact(read))) return rc;
-      compact_at = -1;   // (a prediction for the old block)
-    }
-    nb = std::max(1, std::min(MS_BATCH, need_after));
-    // end the batch where the block is predicted to narrow
-    if (compact_on && s > 1 && compact_at > it && compact_at < it + nb) nb = compact_at - it;
   }
-  // the last step of columns still active at maxiter (a no-op when all stopped)
-  if (trace) std::fprintf(stderr, "[ms] loop end: launched %d\n", it);
-  hipLaunchKernelGGL(ms_cg2_close_kernel, dim3(1), dim3(256), 0, str, sc[it & 1], sh,
-                     (const double*)dshift, S, s, nbd);
+};
+
+// The run's workspaces (grown on demand) and the start block of width s in ms_blk[0].
+static int ms_alloc(MsDev& d, int s, int nrhs, int kind, bool gfin) {
+  gpmi_sp* sp = d.sp;
+  const int64_t n = d.n;
+  const int S = d.S, nbd = d.nbd;
+  auto even = [](size_t x) { return (x + 1) & ~(size_t)1; };
+  if (int rc = grow(&sp->ms_ws, &sp->ms_ws_doubles,
+                    even((size_t)n * nbd) + even((size_t)n * nrhs)))
+    return rc;
+  d.Bd = sp->ms_ws;
+  d.Hs = d.Bd + even((size_t)n * nbd);
+  const size_t c_sp = (size_t)(kind == 5 ? sp->win_nblk : MS_DOT_BLK) * 2 * s;
+  const size_t c_red = 2 * (size_t)s + (size_t)nbd * s;
+  const size_t c_init = (size_t)MS_NBLK * ((size_t)nbd * s + s);
+  if (int rc = grow(&sp->cg2_buf, &sp->cg2_doubles, c_sp + c_red + c_init + S + 2)) return rc;
+  d.spart = sp->cg2_buf;
+  d.dred = d.spart + c_sp;
+  d.ipart = d.dred + c_red;
+  d.dshift = d.ipart + c_init;
+  if (int rc = grow(&sp->ms_blk[0], &sp->ms_blk_doubles[0],
+                    ms_carve(nullptr, n, s, nbd, S, nullptr)))
+    return rc;
+  d.buf = 0;
+  d.blk.sh.flags = reinterpret_cast<int*>(d.dshift + S);
+  d.blk.sh.it_stop = reinterpret_cast<int*>(d.dshift + S + 1);
+  ms_carve(sp->ms_blk[0], n, s, nbd, S, &d.blk);
+  // the dropped columns' final Grams, on the device until the end
+  if (gfin)
+    if (int rc = grow(&sp->ms_gfin, &sp->ms_gfin_doubles, (size_t)S * nbd * s)) return rc;
+  if (!sp->ms_pin) {
+    // coherent: the batch's last update kernel stores the end state into it directly
+    SP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sp->ms_pin), 2 * sizeof(MsPin),
+                         hipHostMallocCoherent | hipHostMallocMapped));
+    for (hipEvent_t* e : {&sp->ms_ev[0], &sp->ms_ev[1]})
+      SP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+  }
+  d.pin_host = reinterpret_cast<MsPin*>(sp->ms_pin);
+  d.pin_dev = nullptr;
+  SP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&d.pin_dev), sp->ms_pin, 0));
+  return 0;
+}
+
+// B (every column of the host block, in device row order), r_0 = its columns from c_lo,
+// s_{-1} = 0, the shifts, and the scalars' start (ms_init_kernel).
+static int ms_start(MsDev& d, const double* etas, const double* rhs, int64_t ld, int nrhs,
+                    int c_lo, bool full) {
+  gpmi_sp* sp = d.sp;
+  hipStream_t str = d.str;
+  const int64_t n = d.n;
+  const int S = d.S, nbd = d.nbd, s = d.blk.s;
+  const int64_t ns = n * s;
+  const double* Hsrc = d.Hs;
+  if (!rhs) {
+    Hsrc = sp->rhs_dev;
+  } else if (ld == nrhs) {
+    SP_TRY(hipMemcpyAsync(d.Hs, rhs, sizeof(double) * n * nrhs, hipMemcpyHostToDevice, str));
+  } else {
+    std::vector<double> h((size_t)n * nrhs);
+    for (int64_t i = 0; i < n; ++i)
+      for (int c = 0; c < nrhs; ++c) h[(size_t)i * nrhs + c] = rhs[i * ld + c];
+    SP_TRY(hipMemcpyAsync(d.Hs, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, str));
+    SP_TRY(hipStreamSynchronize(str));
+  }
+  hipLaunchKernelGGL(rows_gather_kernel, dim3(grid_ns(n, nbd)), dim3(256), 0, str, Hsrc, nrhs,
+                     (const int*)sp->perm_d, n, nbd, d.Bd);
+  SP_LAUNCH("rows_gather_kernel");
+  std::vector<double> hd(S);
+  for (int j = 0; j < S; ++j) hd[j] = etas[j] - d.eta0;
+  SP_TRY(hipMemcpyAsync(d.dshift, hd.data(), sizeof(double) * S, hipMemcpyHostToDevice, str));
+  if (full) {
+    SP_TRY(hipMemcpyAsync(d.blk.R, d.Bd, sizeof(double) * ns, hipMemcpyDeviceToDevice, str));
+  } else {
+    hipLaunchKernelGGL(rows_gather_kernel, dim3(grid_ns(n, s)), dim3(256), 0, str, d.Bd + c_lo,
+                       nbd, (const int*)nullptr, n, s, d.blk.R);
+    SP_LAUNCH("rows_gather_kernel");
+  }
+  // s_{-1} = 0 (beta_{-1} = 0 multiplies it: no NaN may stand there)
+  SP_TRY(hipMemsetAsync(d.blk.S, 0, sizeof(double) * ns, str));
+  launch_ms_dots(d.Bd, d.blk.R, n, s, d.ipart, MS_NBLK, str, nbd);
+  SP_LAUNCH("ms_dots_partial_kernel");
+  hipLaunchKernelGGL(ms_init_kernel, dim3(1), dim3(1024), 0, str, d.blk.sc[0], d.blk.sh,
+                     (const double*)d.ipart, MS_NBLK, S, s, nbd, d.pin_dev);
+  SP_LAUNCH("ms_init_kernel");
+  return 0;
+}
+
+// The last step of columns still active at maxiter (a no-op when all stopped), then G:
+// each original column from the final block, or from the final Grams its compaction
+// scattered when it was dropped.
+static int ms_finish(MsDev& d, const MsRun& run, int nrhs, int nsub, bool trace, double* G,
+                     int* iterations) {
+  gpmi_sp* sp = d.sp;
+  hipStream_t str = d.str;
+  const int S = d.S, nbd = d.nbd, s0 = d.s0, s = d.blk.s, it = run.launched;
+  const MsScal& cur = d.blk.sc[it & 1];
+  const MsShift& sh = d.blk.sh;
+  hipLaunchKernelGGL(ms_cg2_close_kernel, dim3(1), dim3(256), 0, str, cur, sh,
+                     (const double*)d.dshift, S, s, nbd);
   SP_LAUNCH("ms_cg2_close_kernel");
   int flag = 0, it_stop = -1;
-  SP_TRY(hipMemcpyAsync(hact.data(), sc[it & 1].active, sizeof(int) * s, hipMemcpyDeviceToHost, str));
+  std::vector<int> hact(s);
+  SP_TRY(hipMemcpyAsync(hact.data(), cur.active, sizeof(int) * s, hipMemcpyDeviceToHost, str));
   SP_TRY(hipMemcpyAsync(&flag, sh.flags, sizeof(int), hipMemcpyDeviceToHost, str));
   SP_TRY(hipMemcpyAsync(&it_stop, sh.it_stop, sizeof(int), hipMemcpyDeviceToHost, str));
   std::vector<double> hg((size_t)S * nbd * s);
   SP_TRY(hipMemcpyAsync(hg.data(), sh.g, sizeof(double) * hg.size(), hipMemcpyDeviceToHost, str));
   std::vector<double> g_final;   // [j][cp][c original], the dropped columns' entries
-  if (compactions > 0) {
+  if (run.compactions > 0) {
     g_final.resize((size_t)S * nbd * s0);
     SP_TRY(hipMemcpyAsync(g_final.data(), sp->ms_gfin, sizeof(double) * g_final.size(),
                           hipMemcpyDeviceToHost, str));
   }
   SP_TRY(hipStreamSynchronize(str));
-  sp->last_compactions = compactions;
-  segments.emplace_back(s, it - seg_start);
-  sp->last_segments = segments;
+  sp->last_compactions = run.compactions;
+  sp->last_segments = run.segments;
   if (flag)
     return set_error(1, "multi-shift CG: p^T (K + min(eta) I) p <= 0 (not positive definite)");
   bool any = false;
   for (int c = 0; c < s; ++c) any = any || hact[c];
   sp->last_converged = any ? 0 : 1;
-  // each original column from the current block, or from the final Grams its
-  // compaction scattered when it was dropped
   std::vector<int> where(s0, -1);
-  for (int c = 0; c < s; ++c) where[orig[c]] = c;
+  for (int c = 0; c < s; ++c) where[run.orig[c]] = c;
   for (int j = 0; j < S; ++j)
     for (int a = 0; a < nrhs; ++a)
       for (int c = 0; c < nsub; ++c) {
@@ -1812,9 +1527,60 @@ static int msgram_cg2(gpmi_sp* sp, const double* etas, int neta, const double* r
         G[((size_t)j * nrhs + a) * nsub + c] =
             where[c] >= 0 ? hg[jc * s + where[c]] : g_final[jc * s0 + c];
       }
-  if (trace) std::fprintf(stderr, "[ms] all stopped at %d, %d compactions\n", it_stop, compactions);
+  if (trace)
+    std::fprintf(stderr, "[ms] all stopped at %d, %d compactions\n", it_stop, run.compactions);
   if (iterations) *iterations = it_stop >= 0 ? it_stop : it;
   return 0;
+}
+
+static int msgram_cg2(gpmi_sp* sp, const double* etas, int neta, const double* rhs,
+                      int64_t ld, int nrhs, int c_lo, int c_hi, double rtol, int maxiter,
+                      double* G, int* iterations) {
+  const int nsub = c_hi - c_lo;
+  const bool full = nsub == nrhs;
+  Guard g(sp->device);
+  int s = nsub;
+  int kind = 0;
+  if (int rc = spmm_kind(sp, s, &kind)) return rc;
+  // Padding (the Gram of the real columns is unchanged by a zero column, inactive
+  // from the start: ||b|| = 0): the window SpMM at s = 11 stages 12-column rows with
+  // 16-byte loads: cfg 5 s = 11 88 -> 73 us per launch (round 3)
+  if (full && kind == 5 && s == 11 && neta * (s + 1) <= 1024) ++s;
+  if (int rc = spmm_kind(sp, s, &kind)) return rc;
+  if (!sp->ms_stream) {
+    // the CG's own stream, at the same (normal) dispatch priority as the Lanczos's.
+    // Round 5 gave it the high priority (cfg 5 11.85 -> 11.46 ms, when the CG alone took
+    // 8.8 ms); since the compaction the CG alone takes 6.4 ms and a starved Lanczos (4.1
+    // ms alone) plus its host-side quadrature became the step's tail: round 6 alternating
+    // runs, high / normal / low: cfg 5 9.80-9.92 / 9.40-9.44 / 9.77-10.05 ms, cfg 4
+    // 2.86-2.90 / 2.80-2.82 / 2.83-2.86 ms.
+    SP_TRY(hipStreamCreateWithFlags(&sp->ms_stream, hipStreamNonBlocking));
+  }
+  // GPMI_MS_COMPACT=0: no active-column compaction
+  const char* cenv = std::getenv("GPMI_MS_COMPACT");
+  const bool compact_on = !(cenv && std::atoi(cenv) == 0);
+  // GPMI_MS_TRACE=1: each batch's size and each read's prediction on stderr (diagnostic)
+  const bool trace = std::getenv("GPMI_MS_TRACE") != nullptr;
+  MsDev dev{};
+  dev.sp = sp;
+  dev.str = sp->ms_stream;
+  dev.n = sp->n;
+  dev.S = neta;
+  dev.nbd = full ? s : nrhs;
+  dev.s0 = s;
+  dev.eta0 = *std::min_element(etas, etas + neta);
+  dev.rtol = rtol;
+  sp->last_converged = 0;
+  if (int rc = ms_alloc(dev, s, nrhs, kind, compact_on && s > 1)) return rc;
+  if (int rc = ms_start(dev, etas, rhs, ld, nrhs, c_lo, full)) return rc;
+  MsRun run;
+  const int rc = ms_schedule(dev, s, rtol, maxiter, compact_on, trace, &run);
+  if (run.indefinite) {
+    SP_TRY(hipStreamSynchronize(dev.str));
+    return set_error(1, "multi-shift CG: p^T (K + min(eta) I) p <= 0 (not positive definite)");
+  }
+  if (rc) return rc;
+  return ms_finish(dev, run, nrhs, nsub, trace, G, iterations);
 }
 
 // Multi-shift CG Gram blocks for the right-hand sides B[:, c_lo:c_hi] of the nb-column
@@ -2053,7 +1819,7 @@ int gpmi_sp_bench_spmm(gpmi_sp* sp, int s, int reps, double eta, double* avg_ms)
   if (s < 1 || s > 64 || reps < 1) return set_error(-1103, "s in [1, 64], reps >= 1");
   Guard g(sp->device);
   const int64_t ns = sp->n * s;
-  int rc = ensure_ws(sp, (size_t)2 * ns);
+  int rc = grow(&sp->ws, &sp->ws_doubles, (size_t)2 * ns);
   if (rc) return rc;
   hipLaunchKernelGGL(rademacher_kernel, dim3(grid_ns(sp->n, s)), dim3(256), 0, sp->stream, sp->ws,
                      sp->n, s, 12345ull, 0, 1.0, (const int*)nullptr);
