@@ -18,6 +18,7 @@
 #include <vector>
 
 #include "gpmi_internal.h"
+#include "gpmi_host.h"
 #include "gpmi_band.h"
 #include "../../include/gpmi.h"
 
@@ -35,37 +36,9 @@ int set_err(int code, const char* fmt, ...) {
   return code;
 }
 
-#define HIP_TRY(expr)                                                              \
-  do {                                                                             \
-    hipError_t e_ = (expr);                                                        \
-    if (e_ != hipSuccess)                                                          \
-      return set_err(-(int)e_, "%s failed: %s", #expr, hipGetErrorString(e_));     \
-  } while (0)
-
-#define LAUNCH_CHECK(name)                                                         \
-  do {                                                                             \
-    hipError_t e_ = hipGetLastError();                                             \
-    if (e_ != hipSuccess)                                                          \
-      return set_err(-(int)e_, "launch of %s failed: %s", name,                    \
-                     hipGetErrorString(e_));                                       \
-  } while (0)
-
 constexpr int TS = GPMI_TS;
 constexpr int RLD = GPMI_RHS_LD;
 constexpr int OUT_LD = 1 + RLD * RLD;
-
-struct DeviceGuard {
-  int prev = -1;
-  explicit DeviceGuard(int dev) {
-    (void)hipGetDevice(&prev);
-    if (prev != dev) (void)hipSetDevice(dev);
-  }
-  ~DeviceGuard() {
-    int cur = -1;
-    (void)hipGetDevice(&cur);
-    if (prev >= 0 && cur != prev) (void)hipSetDevice(prev);
-  }
-};
 
 }  // namespace
 

@@ -1,7 +1,9 @@
-// Band path (gpmi_band.hip, gpmi_band_api.hip): constants and kernel declarations.
+// Band path (gpmi_band.hip and the host side, gpmi_band_*.hip): constants and kernel
+// declarations.
 #pragma once
 
 #include "gpmi_internal.h"
+#include "gpmi_band_plan.h"   // symm_chunk, CHASE_MSG (HIP-free: shared with the host check)
 
 namespace gpmi {
 
@@ -17,26 +19,6 @@ constexpr int HH_PANEL_LDS = 96 * 1024;  // dynamic LDS: one hh_panel workgroup 
 constexpr int HH_PART_LD = 136;    // partial record: S_j (j < 128), sum x^2 at [128]
 constexpr int QT_ROWS = 64;        // rows per qt_partial / qt_apply workgroup
 constexpr int TN_CH = 128;         // rows per tn_partial chunk
-constexpr int SY_CH = 16;          // tile columns per symm split-K chunk (at most)
-// symm split-K chunk for an mt-tile trailing block on `slots` resident workgroups (two
-// per CU): the mt x ceil(mt / chunk) workgroups run in ceil(W / slots) rounds of chunk
-// 128^3 products each, so the chunk minimising rounds x chunk (+ the partial sums'
-// reads, ~1/620 of a product each) ends the grid in full rounds: at mt = 117, chunk 9
-// (1521 workgroups, 2.97 rounds of 512) instead of mt^2 / 1024 = 13 (1053, 2.06 rounds
-// run as 3: the third nearly empty, 1.06 ms against ~0.73).
-inline int symm_chunk(int mt, int slots) {
-  int best = 1;
-  long long bc = -1;
-  for (int ch = 1; ch <= SY_CH; ++ch) {
-    const long long w = (long long)mt * ((mt + ch - 1) / ch);
-    const long long c = (w + slots - 1) / slots * ch * 620 + w;
-    if (bc < 0 || c <= bc) {
-      bc = c;
-      best = ch;
-    }
-  }
-  return best;
-}
 constexpr int BAND_ULD = 384;      // U = [W | V | W]
 // CUs the pipelined look-ahead SYR2K (one workgroup per CU) leaves to the next panel's
 // CholeskyQR chain, whose single-workgroup kernels need a whole CU (N = 16384:
@@ -153,7 +135,6 @@ __global__ void cq_top_kernel(double* Lx, const double* Linv, const int* flags, 
 __global__ void band_der_kernel(const double* fac, int nt, double* ysol, double* der);
 
 __global__ void chase_copy_kernel(const double* Ab, double* A, int64_t lda, int n);
-constexpr int CHASE_MSG = 136;   // = CMSG (gpmi_chase.hip): values per hand-off slot
 constexpr int CHASE_THREADS = 512;   // = SCT (gpmi_chase.hip): systolic chase workgroup
 #ifndef GPMI_CHASE_SPLIT_THREADS
 #define GPMI_CHASE_SPLIT_THREADS 512

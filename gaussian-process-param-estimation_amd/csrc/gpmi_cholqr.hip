@@ -1,4 +1,4 @@
-// CholeskyQR panel of the band reduction (the default panel; gpmi_band_api.hip
+// CholeskyQR panel of the band reduction (the default panel; gpmi_band_reduce.hip
 // falls back to the Householder panel of gpmi_band.hip when it reports failure).
 //
 // The Householder panel QR needs one grid-wide reduction per column (128 per
@@ -15,7 +15,7 @@
 // (I - V T V^T)^T P = [S R; 0]. Only the 128 x 128 top block of Q needs the
 // sequential LU; the rows below are V_2 = Q_2 U^-1, one MFMA tile product each.
 //
-// Kernels (one panel; host sequence in gpmi_band_api.hip: cq_panel):
+// Kernels (one panel; host sequence in gpmi_band_reduce.hip: cq_panel):
 //   cq_gram_kernel     (m/64 tiles)     Gram partials of P's row tiles (packed lower)
 //   cq_reduce_kernel                    G = sum of the partials
 //   cq_chol_kernel     (1 workgroup)    L = chol(G [+ s I]), L^-1; failure flag

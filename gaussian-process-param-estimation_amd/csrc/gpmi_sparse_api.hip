@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "gpmi_internal.h"
+#include "gpmi_host.h"
 #include "gpmi_sparse.h"
 #include "gpmi_ms_sched.h"
 #include "gpmi_band.h"
@@ -38,47 +39,12 @@ wing_table(std::integer_sequence<int, I...>) {
 const auto kWing = wing_table(std::make_integer_sequence<int, WING_MAXS>{});
 int op_view(const gpmi_op* op, OpView* v);            // gpmi_api.hip
 int matern_params_host(double nu, MaternParams* P);   // gpmi_api.hip
-int set_error(int code, const char* msg);             // gpmi_api.hip
 }  // namespace gpmi
 
 namespace {
 
-#define SP_TRY(expr)                                                                   \
-  do {                                                                                 \
-    hipError_t e_ = (expr);                                                            \
-    if (e_ != hipSuccess) {                                                            \
-      char b_[400];                                                                    \
-      snprintf(b_, sizeof(b_), "%s failed: %s", #expr, hipGetErrorString(e_));        \
-      return set_error(-(int)e_, b_);                                                  \
-    }                                                                                  \
-  } while (0)
-
-#define SP_LAUNCH(name)                                                                \
-  do {                                                                                 \
-    hipError_t e_ = hipGetLastError();                                                 \
-    if (e_ != hipSuccess) {                                                            \
-      char b_[400];                                                                    \
-      snprintf(b_, sizeof(b_), "launch of %s failed: %s", name, hipGetErrorString(e_)); \
-      return set_error(-(int)e_, b_);                                                  \
-    }                                                                                  \
-  } while (0)
-
 constexpr int NBLK = 256;   // fixed reduction grid (deterministic sums)
 constexpr int MAXS = 32;    // vector-block width per device pass
-
-struct Guard {
-  int prev = -1;
-  explicit Guard(int d) {
-    (void)hipGetDevice(&prev);
-    if (prev != d) (void)hipSetDevice(d);
-  }
-  ~Guard() {
-    int c = -1;
-    (void)hipGetDevice(&c);
-    if (prev >= 0 && c != prev) (void)hipSetDevice(prev);
-  }
-};
-
 
 }  // namespace
 
@@ -180,10 +146,10 @@ namespace {
 // now; the contents do not survive a growth).
 int grow(double** buf, size_t* have, size_t need) {
   if (*have >= need) return 0;
-  if (*buf) SP_TRY(hipFree(*buf));
+  if (*buf) HIP_TRY(hipFree(*buf));
   *buf = nullptr;
   *have = 0;
-  SP_TRY(hipMalloc(buf, sizeof(double) * need));
+  HIP_TRY(hipMalloc(buf, sizeof(double) * need));
   *have = need;
   return 0;
 }
@@ -210,16 +176,16 @@ int ensure_window(gpmi_sp* sp) {
 
 int build_window(gpmi_sp* sp) {
   const int64_t nblk = (sp->n + WIN_ROWS - 1) / WIN_ROWS;
-  SP_TRY(hipMalloc(&sp->win_cols, sizeof(int) * (size_t)nblk * WIN_MAXU));
-  SP_TRY(hipMalloc(&sp->win_u, sizeof(int) * (size_t)nblk));
-  SP_TRY(hipMalloc(&sp->win_lidx, sizeof(unsigned short) * (size_t)std::max<int64_t>(1, sp->nnz)));
+  HIP_TRY(hipMalloc(&sp->win_cols, sizeof(int) * (size_t)nblk * WIN_MAXU));
+  HIP_TRY(hipMalloc(&sp->win_u, sizeof(int) * (size_t)nblk));
+  HIP_TRY(hipMalloc(&sp->win_lidx, sizeof(unsigned short) * (size_t)std::max<int64_t>(1, sp->nnz)));
   hipLaunchKernelGGL(spmm_window_build_kernel, dim3((unsigned)nblk), dim3(256), 0, sp->stream,
                      sp->indptr, sp->indices, sp->n, sp->win_cols, sp->win_u, sp->win_lidx);
-  SP_LAUNCH("spmm_window_build_kernel");
+  LAUNCH_CHECK("spmm_window_build_kernel");
   std::vector<int> hu((size_t)nblk);
-  SP_TRY(hipMemcpyAsync(hu.data(), sp->win_u, sizeof(int) * nblk, hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(hu.data(), sp->win_u, sizeof(int) * nblk, hipMemcpyDeviceToHost,
                         sp->stream));
-  SP_TRY(hipStreamSynchronize(sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
   int mu = 0;
   for (int v : hu) mu = std::max(mu, v);
   {
@@ -228,7 +194,7 @@ int build_window(gpmi_sp* sp) {
     sp->win_mean = su / (double)nblk;
   }
   std::vector<int64_t> hp((size_t)sp->n + 1);
-  SP_TRY(hipMemcpy(hp.data(), sp->indptr, sizeof(int64_t) * (sp->n + 1), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(hp.data(), sp->indptr, sizeof(int64_t) * (sp->n + 1), hipMemcpyDeviceToHost));
   int mm = 0;
   for (int64_t b = 0; b < nblk; ++b)
     if (hu[(size_t)b] > 0) {
@@ -254,10 +220,10 @@ int build_window(gpmi_sp* sp) {
   sp->win_use = lds <= 32 * 1024;
   if (lds > 160 * 1024) return set_error(-1104, "spmm window exceeds LDS");
   if (lds > 64 * 1024)
-    SP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&csr_spmm_win_kernel),
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(&csr_spmm_win_kernel),
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   for (auto f : kWing)
-    SP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(f),
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(f),
                                hipFuncAttributeMaxDynamicSharedMemorySize, WING_MAX_LDS));
   sp->win_nblk = nblk;
   sp->win_maxu.store(mu, std::memory_order_release);
@@ -314,11 +280,11 @@ int spmm_launch(gpmi_sp* sp, const double* X, double* Y, int s, double eta, hipS
     else
       hipLaunchKernelGGL(dense_mm_kernel<2>, grid, dim3(256), 0, st, sp->dK, sp->dld, sp->n, X, s,
                          sp->dkcs, Yp);
-    SP_LAUNCH("dense_mm_kernel");
+    LAUNCH_CHECK("dense_mm_kernel");
     const int64_t ns = sp->n * s;
     hipLaunchKernelGGL(dense_mm_reduce_kernel, dim3((unsigned)((ns + 255) / 256)), dim3(256), 0, st,
                        Yp, sp->dsplit, ns, X, eta, Y);
-    SP_LAUNCH("dense_mm_reduce_kernel");
+    LAUNCH_CHECK("dense_mm_reduce_kernel");
     return 0;
   }
   int kind = 0;
@@ -339,7 +305,7 @@ int spmm_launch(gpmi_sp* sp, const double* X, double* Y, int s, double eta, hipS
     hipLaunchKernelGGL(kfn, dim3((unsigned)sp->win_nblk), dim3(64 * tpr), lds, st, sp->indptr,
                        sp->indices, sp->win_lidx, sp->data, sp->n, sp->win_cols, sp->win_u, X, Y,
                        eta, pqp, dots2, stamp);
-    SP_LAUNCH("csr_spmm_wing_kernel");
+    LAUNCH_CHECK("csr_spmm_wing_kernel");
     if (pqp && pq_blocks) *pq_blocks = (int)sp->win_nblk;
     return 0;
   }
@@ -352,7 +318,7 @@ int spmm_launch(gpmi_sp* sp, const double* X, double* Y, int s, double eta, hipS
                        dim3((unsigned)sp->win_nblk),
                        dim3(256), lds, st, sp->indptr, sp->indices, sp->win_lidx, sp->data,
                        sp->n, sp->win_cols, sp->win_u, X, (int64_t)s, Y, (int64_t)s, s, eta);
-    SP_LAUNCH("csr_spmm_win_kernel");
+    LAUNCH_CHECK("csr_spmm_win_kernel");
     return 0;
   }
   if (kind == 3 && (reinterpret_cast<uintptr_t>(X) & 15) == 0 &&
@@ -361,13 +327,13 @@ int spmm_launch(gpmi_sp* sp, const double* X, double* Y, int s, double eta, hipS
     // 132.5 us per s = 20 launch)
     hipLaunchKernelGGL(csr_spmm_pair_kernel<3>, dim3((unsigned)((sp->n + 3) / 4)), dim3(256), 0, st,
                        sp->indptr, sp->indices, sp->data, sp->n, X, Y, s, 64 / (s / 2), eta);
-    SP_LAUNCH("csr_spmm_pair_kernel");
+    LAUNCH_CHECK("csr_spmm_pair_kernel");
     return 0;
   }
   hipLaunchKernelGGL(csr_spmm_kernel, dim3((unsigned)((sp->n + 3) / 4)), dim3(256), 0,
                      st, sp->indptr, sp->indices, sp->data, sp->n, X, (int64_t)s, Y,
                      (int64_t)s, s, 64 / s, eta);
-  SP_LAUNCH("csr_spmm_kernel");
+  LAUNCH_CHECK("csr_spmm_kernel");
   return 0;
 }
 
@@ -377,7 +343,7 @@ int take_event(gpmi_sp* sp, hipEvent_t* e) {
     sp->ev_pool.pop_back();
     return 0;
   }
-  SP_TRY(hipEventCreateWithFlags(e, gpmi::timing_event_flags()));
+  HIP_TRY(hipEventCreateWithFlags(e, gpmi::timing_event_flags()));
   return 0;
 }
 
@@ -406,11 +372,11 @@ int spmm(gpmi_sp* sp, const double* X, double* Y, int s, double eta, hipStream_t
       if (int rc = take_event(sp, &rec.e1)) return rc;
     }
   }
-  if (rec.slot < 0) SP_TRY(hipEventRecord(rec.e0, st));
+  if (rec.slot < 0) HIP_TRY(hipEventRecord(rec.e0, st));
   if (int rc = spmm_launch(sp, X, Y, s, eta, st, pqp, pq_blocks, dots2,
                            rec.slot >= 0 ? sp->stamps + 2 * sp->win_nblk * rec.slot : nullptr))
     return rc;
-  if (rec.slot < 0) SP_TRY(hipEventRecord(rec.e1, st));
+  if (rec.slot < 0) HIP_TRY(hipEventRecord(rec.e1, st));
   std::lock_guard<std::mutex> lock(sp->timing_mu);
   sp->spmm_log.push_back(rec);
   return 0;
@@ -427,10 +393,10 @@ int col_dots(gpmi_sp* sp, const double* A, int64_t strideA, int J, const double*
   if (!st) st = sp->stream;
   hipLaunchKernelGGL(col_dot_partial_kernel, dim3(NBLK, J), dim3(256), 0, st, A, strideA,
                      B, sp->n, s, partial);
-  SP_LAUNCH("col_dot_partial_kernel");
+  LAUNCH_CHECK("col_dot_partial_kernel");
   hipLaunchKernelGGL(col_dot_reduce_kernel, dim3((J * s + 3) / 4), dim3(256), 0, st,
                      partial, NBLK, J, s, out);
-  SP_LAUNCH("col_dot_reduce_kernel");
+  LAUNCH_CHECK("col_dot_reduce_kernel");
   return 0;
 }
 
@@ -473,7 +439,7 @@ int lanczos_block(gpmi_sp* sp, double* V, double* W, int s, int steps, double* h
   double* nb = na + MAXS;
   int* dead = reinterpret_cast<int*>(nb + MAXS);
   // one pass (orth = 0): the second pass's coefficients stay zero
-  if (orth == 0) SP_TRY(hipMemsetAsync(H2, 0, sizeof(double) * MAXS, sp->stream));
+  if (orth == 0) HIP_TRY(hipMemsetAsync(H2, 0, sizeof(double) * MAXS, sp->stream));
   for (int k = 0; k < steps; ++k) {
     double* Vk = V + (int64_t)k * ns;
     const int jlo = orth < 0 ? 0 : std::max(0, k - orth);   // projection window [jlo, k]
@@ -483,7 +449,7 @@ int lanczos_block(gpmi_sp* sp, double* V, double* W, int s, int steps, double* h
     if (k > 0) {   // W -= beta_{k-1} V_{k-1}
       hipLaunchKernelGGL(col_axpby_kernel, dim3(grid_ns(sp->n, s)), dim3(256), 0, sp->stream,
                          V + (int64_t)(k - 1) * ns, W, na, nb, sp->n, s);
-      SP_LAUNCH("col_axpby_kernel");
+      LAUNCH_CHECK("col_axpby_kernel");
     }
     for (int pass = 0; pass < (orth == 0 ? 1 : 2); ++pass) {   // CGS(2) against V_jlo .. V_k
       double* H = pass == 0 ? H1 : H2;
@@ -491,28 +457,28 @@ int lanczos_block(gpmi_sp* sp, double* V, double* W, int s, int steps, double* h
       if (rc) return rc;
       hipLaunchKernelGGL(col_gs_update_kernel, dim3((unsigned)((ns + 511) / 512)), dim3(256), 0,
                          sp->stream, W, V + (int64_t)jlo * ns, ns, H, J, sp->n, s);
-      SP_LAUNCH("col_gs_update_kernel");
+      LAUNCH_CHECK("col_gs_update_kernel");
     }
     rc = col_dots(sp, W, 0, 1, W, s, nrm);
     if (rc) return rc;
     hipLaunchKernelGGL(lanczos_scalar_kernel, dim3(1), dim3(64), 0, sp->stream,
                        H1 + (size_t)(k - jlo) * s, orth == 0 ? H2 : H2 + (size_t)(k - jlo) * s,
                        nrm, s, k, steps, dead, dalpha, dbeta, ca, cb, na, nb);
-    SP_LAUNCH("lanczos_scalar_kernel");
+    LAUNCH_CHECK("lanczos_scalar_kernel");
     if (k + 1 < steps) {
       // V_{k+1} = W / beta  (b = 0 -> X * 0 + 0 * Y; Y is zero-initialised below)
       double* Vn = V + (int64_t)(k + 1) * ns;
-      SP_TRY(hipMemsetAsync(Vn, 0, sizeof(double) * ns, sp->stream));
+      HIP_TRY(hipMemsetAsync(Vn, 0, sizeof(double) * ns, sp->stream));
       hipLaunchKernelGGL(col_axpby_kernel, dim3(grid_ns(sp->n, s)), dim3(256), 0, sp->stream, W,
                          Vn, ca, cb, sp->n, s);
-      SP_LAUNCH("col_axpby_kernel");
+      LAUNCH_CHECK("col_axpby_kernel");
     }
   }
-  SP_TRY(hipMemcpyAsync(h_alpha, dalpha, sizeof(double) * s * steps, hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(h_alpha, dalpha, sizeof(double) * s * steps, hipMemcpyDeviceToHost,
                         sp->stream));
-  SP_TRY(hipMemcpyAsync(h_beta, dbeta, sizeof(double) * s * steps, hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(h_beta, dbeta, sizeof(double) * s * steps, hipMemcpyDeviceToHost,
                         sp->stream));
-  SP_TRY(hipStreamSynchronize(sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
   return 0;
 }
 
@@ -537,9 +503,9 @@ int lanczos_block_plain(gpmi_sp* sp, double* U, double* Y, int s, int steps, dou
   if (rc) return rc;
   double* pq = sp->partial;                 // [s][nb]: u_k . y
   double* pv = pq + (size_t)nb * s;         // [2][s][nb]: ||u_{k+1}||^2, u_{k+1} . u_k
-  SP_TRY(hipMemsetAsync(dbe, 0, sizeof(double) * s * steps, sp->stream));
+  HIP_TRY(hipMemsetAsync(dbe, 0, sizeof(double) * s * steps, sp->stream));
   // u_{-1}: zero (its coefficient is 0 at k = 0; 0 * garbage could be NaN)
-  SP_TRY(hipMemsetAsync(U + 2 * ns, 0, sizeof(double) * ns, sp->stream));
+  HIP_TRY(hipMemsetAsync(U + 2 * ns, 0, sizeof(double) * ns, sp->stream));
   const unsigned sgrid = (unsigned)s;   // lz0_alpha_kernel: one workgroup per column
   for (int k = 0; k < steps; ++k) {
     double* Uc = U + (int64_t)(k % 3) * ns;
@@ -551,23 +517,23 @@ int lanczos_block_plain(gpmi_sp* sp, double* U, double* Y, int s, int steps, dou
     if (pqb != nb) {
       hipLaunchKernelGGL(lz0_dot64_kernel, dim3((unsigned)nb), dim3(256), 0, sp->stream, Uc, Y, n,
                          s, pq);
-      SP_LAUNCH("lz0_dot64_kernel");
+      LAUNCH_CHECK("lz0_dot64_kernel");
     }
     hipLaunchKernelGGL(lz0_alpha_kernel, dim3(sgrid), dim3(256), 0, sp->stream, pq, pv, nb, s, k,
                        steps, st, dead, dal, dbe, coef);
-    SP_LAUNCH("lz0_alpha_kernel");
+    LAUNCH_CHECK("lz0_alpha_kernel");
     hipLaunchKernelGGL(lz0_update_kernel, dim3((unsigned)nb), dim3(256), 0, sp->stream, Y, Up, Uc,
                        Un, coef, n, s, pv);
-    SP_LAUNCH("lz0_update_kernel");
+    LAUNCH_CHECK("lz0_update_kernel");
   }
   hipLaunchKernelGGL(lz0_alpha_kernel, dim3(sgrid), dim3(256), 0, sp->stream, pq, pv, nb, s, steps,
                      steps, st, dead, dal, dbe, coef);
-  SP_LAUNCH("lz0_alpha_kernel");
-  SP_TRY(hipMemcpyAsync(h_alpha, dal, sizeof(double) * s * steps, hipMemcpyDeviceToHost,
+  LAUNCH_CHECK("lz0_alpha_kernel");
+  HIP_TRY(hipMemcpyAsync(h_alpha, dal, sizeof(double) * s * steps, hipMemcpyDeviceToHost,
                         sp->stream));
-  SP_TRY(hipMemcpyAsync(h_beta, dbe, sizeof(double) * s * steps, hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(h_beta, dbe, sizeof(double) * s * steps, hipMemcpyDeviceToHost,
                         sp->stream));
-  SP_TRY(hipStreamSynchronize(sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
   return 0;
 }
 
@@ -600,9 +566,9 @@ int lanczos_block_dcgs2(gpmi_sp* sp, double* V, double* U, double* Y, int s, int
   const int lz_nb = LZ_NB;
   int rc = grow(&sp->partial, &sp->partial_doubles, (size_t)lz_nb * (2 * steps + 2) * s);
   if (rc) return rc;
-  SP_TRY(hipMemsetAsync(H, 0, sizeof(double) * s * hsz, sp->stream));
-  SP_TRY(hipMemsetAsync(dal, 0, sizeof(double) * 2 * s * steps, sp->stream));
-  SP_TRY(hipMemcpyAsync(U, V, sizeof(double) * ns, hipMemcpyDeviceToDevice, sp->stream));
+  HIP_TRY(hipMemsetAsync(H, 0, sizeof(double) * s * hsz, sp->stream));
+  HIP_TRY(hipMemsetAsync(dal, 0, sizeof(double) * 2 * s * steps, sp->stream));
+  HIP_TRY(hipMemcpyAsync(U, V, sizeof(double) * ns, hipMemcpyDeviceToDevice, sp->stream));
   // non-temporal basis reads for a basis over twice the 256 MB Infinity Cache (cfg 5
   // Lanczos 13.0 -> 11.2 ms; at cfg 4's 0.3 GB they measured slower, 6.8 -> 7.0 ms)
   const bool lz_nt = sizeof(double) * (double)ns * (steps + 1) > 512.0 * 1024 * 1024;
@@ -619,16 +585,16 @@ int lanczos_block_dcgs2(gpmi_sp* sp, double* V, double* U, double* Y, int s, int
       hipLaunchKernelGGL(lz_nt ? lz_dots_kernel<true> : lz_dots_kernel<false>, dim3(lz_nb),
                          dim3(256), 0, sp->stream, V, ns, k, j0, U,
                          last ? (const double*)nullptr : Y, n, s, nv, sp->partial);
-      SP_LAUNCH("lz_dots_kernel");
+      LAUNCH_CHECK("lz_dots_kernel");
     }
     hipLaunchKernelGGL(col_dot_reduce_kernel, dim3((nv * s + 3) / 4), dim3(256), 0, sp->stream,
                        sp->partial, lz_nb, nv, s, d);
-    SP_LAUNCH("col_dot_reduce_kernel");
+    LAUNCH_CHECK("col_dot_reduce_kernel");
     const size_t sdb = sizeof(double) * (size_t)(2 * k + 2) * s;   // the dots in LDS
     const int stage = sdb <= 64 * 1024 ? 1 : 0;
     hipLaunchKernelGGL(lz_scalar_kernel, dim3(1), dim3(1024), stage ? sdb : 0, sp->stream, d, k,
                        steps, s, H, cv, cu, ir, rho, dead, inex, dal, dbe, stage);
-    SP_LAUNCH("lz_scalar_kernel");
+    LAUNCH_CHECK("lz_scalar_kernel");
     if (!last) {
       // four row chunks per thread sharing its two columns' coefficients (cfg 5 Lanczos
       // 13.7 -> 12.65 ms against one): the grid's thread-pair count P with 2 P a
@@ -639,16 +605,16 @@ int lanczos_block_dcgs2(gpmi_sp* sp, double* V, double* U, double* Y, int s, int
       auto kfn = lz_nt ? lz_update_kernel<4, true> : lz_update_kernel<4, false>;
       hipLaunchKernelGGL(kfn, dim3((unsigned)g), dim3(256), 0, sp->stream, V, ns, k, U, Y, cv, cu,
                          ir, s);
-      SP_LAUNCH("lz_update_kernel");
+      LAUNCH_CHECK("lz_update_kernel");
     }
   }
   std::vector<int> hin(s);
-  SP_TRY(hipMemcpyAsync(h_alpha, dal, sizeof(double) * s * steps, hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(h_alpha, dal, sizeof(double) * s * steps, hipMemcpyDeviceToHost,
                         sp->stream));
-  SP_TRY(hipMemcpyAsync(h_beta, dbe, sizeof(double) * s * steps, hipMemcpyDeviceToHost,
+  HIP_TRY(hipMemcpyAsync(h_beta, dbe, sizeof(double) * s * steps, hipMemcpyDeviceToHost,
                         sp->stream));
-  SP_TRY(hipMemcpyAsync(hin.data(), inex, sizeof(int) * s, hipMemcpyDeviceToHost, sp->stream));
-  SP_TRY(hipStreamSynchronize(sp->stream));
+  HIP_TRY(hipMemcpyAsync(hin.data(), inex, sizeof(int) * s, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
   *inexact = false;
   for (int c = 0; c < s; ++c) *inexact = *inexact || hin[c];
   return 0;
@@ -661,19 +627,19 @@ extern "C" {
 int gpmi_sp_create_csr(int device, int64_t n, const int64_t* indptr, const int* indices,
                        const double* data, gpmi_sp** out) {
   if (!out || n <= 0) return set_error(-1100, "invalid arguments");
-  Guard g(device);
+  DeviceGuard g(device);
   gpmi_sp* sp = new gpmi_sp();
   sp->device = device;
   sp->n = n;
   sp->nnz = indptr[n];
-  SP_TRY(hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking));
-  SP_TRY(hipMalloc(&sp->indptr, sizeof(int64_t) * (n + 1)));
-  SP_TRY(hipMalloc(&sp->indices, sizeof(int) * std::max<int64_t>(1, sp->nnz)));
-  SP_TRY(hipMalloc(&sp->data, sizeof(double) * std::max<int64_t>(1, sp->nnz)));
-  SP_TRY(hipMalloc(&sp->small, sizeof(double) * 16384));
-  SP_TRY(hipMemcpy(sp->indptr, indptr, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
-  SP_TRY(hipMemcpy(sp->indices, indices, sizeof(int) * sp->nnz, hipMemcpyHostToDevice));
-  SP_TRY(hipMemcpy(sp->data, data, sizeof(double) * sp->nnz, hipMemcpyHostToDevice));
+  HIP_TRY(hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking));
+  HIP_TRY(hipMalloc(&sp->indptr, sizeof(int64_t) * (n + 1)));
+  HIP_TRY(hipMalloc(&sp->indices, sizeof(int) * std::max<int64_t>(1, sp->nnz)));
+  HIP_TRY(hipMalloc(&sp->data, sizeof(double) * std::max<int64_t>(1, sp->nnz)));
+  HIP_TRY(hipMalloc(&sp->small, sizeof(double) * 16384));
+  HIP_TRY(hipMemcpy(sp->indptr, indptr, sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(sp->indices, indices, sizeof(int) * sp->nnz, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(sp->data, data, sizeof(double) * sp->nnz, hipMemcpyHostToDevice));
   *out = sp;
   return 0;
 }
@@ -685,13 +651,13 @@ int gpmi_sp_create_matern(int device, const double* points, int64_t n, int d,
   MaternParams P;
   int rc = matern_params_host(nu, &P);
   if (rc) return rc;
-  Guard g(device);
+  DeviceGuard g(device);
   gpmi_sp* sp = new gpmi_sp();
   sp->device = device;
   sp->n = n;
   sp->tau = tau;
-  SP_TRY(hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking));
-  SP_TRY(hipMalloc(&sp->small, sizeof(double) * 16384));
+  HIP_TRY(hipStreamCreateWithFlags(&sp->stream, hipStreamNonBlocking));
+  HIP_TRY(hipMalloc(&sp->small, sizeof(double) * 16384));
   hipStream_t st = sp->stream;
   // Scaled-distance cutoff: smallest grid x with matern(x) <= tau, with margin.
   // matern is decreasing, so every pair beyond xcut has matern < tau.
@@ -702,11 +668,11 @@ int gpmi_sp_create_matern(int device, const double* points, int64_t n, int d,
   double* dv = sp->small + M;
   for (int it = 0; it < 60; ++it) {
     for (int i = 0; i < M; ++i) hx[i] = xmax * (i + 1) / M;
-    SP_TRY(hipMemcpyAsync(dx, hx.data(), sizeof(double) * M, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dx, hx.data(), sizeof(double) * M, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(matern_eval_kernel, dim3(M / 256), dim3(256), 0, st, dx, (int64_t)M, P, dv);
-    SP_LAUNCH("matern_eval_kernel");
-    SP_TRY(hipMemcpyAsync(hv.data(), dv, sizeof(double) * M, hipMemcpyDeviceToHost, st));
-    SP_TRY(hipStreamSynchronize(st));
+    LAUNCH_CHECK("matern_eval_kernel");
+    HIP_TRY(hipMemcpyAsync(hv.data(), dv, sizeof(double) * M, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
     int first = -1;
     for (int i = 0; i < M; ++i)
       if (hv[i] <= tau) {
@@ -722,16 +688,16 @@ int gpmi_sp_create_matern(int device, const double* points, int64_t n, int d,
   if (xcut == 0.0) return set_error(-1101, "taper threshold not reached (tau too small)");
   double *dp = nullptr, *ds = nullptr;
   int* dcnt = nullptr;
-  SP_TRY(hipMalloc(&dp, sizeof(double) * n * d));
-  SP_TRY(hipMalloc(&ds, sizeof(double) * 2 * GPMI_MAX_DIM));   // [scale | 1 / scale]
-  SP_TRY(hipMalloc(&dcnt, sizeof(int) * n));
-  SP_TRY(hipMemcpyAsync(dp, points, sizeof(double) * n * d, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMalloc(&dp, sizeof(double) * n * d));
+  HIP_TRY(hipMalloc(&ds, sizeof(double) * 2 * GPMI_MAX_DIM));   // [scale | 1 / scale]
+  HIP_TRY(hipMalloc(&dcnt, sizeof(int) * n));
+  HIP_TRY(hipMemcpyAsync(dp, points, sizeof(double) * n * d, hipMemcpyHostToDevice, st));
   std::vector<double> hsc(2 * GPMI_MAX_DIM, 1.0);
   for (int k = 0; k < d; ++k) {
     hsc[k] = scale[k];
     hsc[GPMI_MAX_DIM + k] = 1.0 / scale[k];
   }
-  SP_TRY(hipMemcpyAsync(ds, hsc.data(), sizeof(double) * hsc.size(), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(ds, hsc.data(), sizeof(double) * hsc.size(), hipMemcpyHostToDevice, st));
   const unsigned grid = (unsigned)((n + 3) / 4);
   // Cell list (d <= 3): cells of width >= xcut * scale_k, so a kept pair is in the
   // same or an adjacent cell; coarsened while there are more cells than 4 n.
@@ -803,49 +769,49 @@ int gpmi_sp_create_matern(int device, const double* points, int64_t n, int d,
         for (const auto& kc : keys)
           for (int q = hstart[kc.second]; q < hstart[kc.second + 1]; ++q) lorder.push_back(hperm[q]);
       }
-      SP_TRY(hipMalloc(&dcell, sizeof(int) * (2 * n + d + total + 1)));
+      HIP_TRY(hipMalloc(&dcell, sizeof(int) * (2 * n + d + total + 1)));
       dgdim = dcell + n;
       dstart = dgdim + d;
       dperm = dstart + total + 1;
-      SP_TRY(hipMemcpyAsync(dcell, hcell.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-      SP_TRY(hipMemcpyAsync(dgdim, hg.data(), sizeof(int) * d, hipMemcpyHostToDevice, st));
-      SP_TRY(hipMemcpyAsync(dstart, hstart.data(), sizeof(int) * (total + 1),
+      HIP_TRY(hipMemcpyAsync(dcell, hcell.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(dgdim, hg.data(), sizeof(int) * d, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipMemcpyAsync(dstart, hstart.data(), sizeof(int) * (total + 1),
                             hipMemcpyHostToDevice, st));
-      SP_TRY(hipMemcpyAsync(dperm, hperm.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-      SP_TRY(hipStreamSynchronize(st));   // host vectors go out of scope
+      HIP_TRY(hipMemcpyAsync(dperm, hperm.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
+      HIP_TRY(hipStreamSynchronize(st));   // host vectors go out of scope
     }
   }
   if (cells) {
     hipLaunchKernelGGL(csr_cell_count_kernel, dim3(grid), dim3(256), 0, st, dp, n, d, ds, P, tau,
                        xcut, dcell, dgdim, dstart, dperm, dcnt);
-    SP_LAUNCH("csr_cell_count_kernel");
+    LAUNCH_CHECK("csr_cell_count_kernel");
   } else {
     hipLaunchKernelGGL(csr_count_kernel, dim3(grid), dim3(256), 0, st, dp, n, d, ds, P, tau, xcut,
                        dcnt);
-    SP_LAUNCH("csr_count_kernel");
+    LAUNCH_CHECK("csr_count_kernel");
   }
   std::vector<int> cnt(n);
-  SP_TRY(hipMemcpyAsync(cnt.data(), dcnt, sizeof(int) * n, hipMemcpyDeviceToHost, st));
-  SP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipMemcpyAsync(cnt.data(), dcnt, sizeof(int) * n, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
   if (cells && *std::max_element(cnt.begin(), cnt.end()) > CELL_CAP_HOST) cells = false;
   std::vector<int64_t> ip(n + 1, 0);
   for (int64_t i = 0; i < n; ++i) ip[i + 1] = ip[i] + cnt[i];
   sp->nnz = ip[n];
-  SP_TRY(hipMalloc(&sp->indptr, sizeof(int64_t) * (n + 1)));
-  SP_TRY(hipMalloc(&sp->indices, sizeof(int) * std::max<int64_t>(1, sp->nnz)));
-  SP_TRY(hipMalloc(&sp->data, sizeof(double) * std::max<int64_t>(1, sp->nnz)));
-  SP_TRY(hipMemcpyAsync(sp->indptr, ip.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice,
+  HIP_TRY(hipMalloc(&sp->indptr, sizeof(int64_t) * (n + 1)));
+  HIP_TRY(hipMalloc(&sp->indices, sizeof(int) * std::max<int64_t>(1, sp->nnz)));
+  HIP_TRY(hipMalloc(&sp->data, sizeof(double) * std::max<int64_t>(1, sp->nnz)));
+  HIP_TRY(hipMemcpyAsync(sp->indptr, ip.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice,
                         st));
   if (cells) {
     hipLaunchKernelGGL(csr_cell_fill_kernel, dim3(grid), dim3(256), 0, st, dp, n, d, ds, P, tau,
                        xcut, dcell, dgdim, dstart, dperm, sp->indptr, sp->indices, sp->data);
-    SP_LAUNCH("csr_cell_fill_kernel");
+    LAUNCH_CHECK("csr_cell_fill_kernel");
   } else {   // all pairs (d > 3, or a row holds more than CELL_CAP kept entries)
     hipLaunchKernelGGL(csr_fill_kernel, dim3(grid), dim3(256), 0, st, dp, n, d, ds, P, tau, xcut,
                        sp->indptr, sp->indices, sp->data);
-    SP_LAUNCH("csr_fill_kernel");
+    LAUNCH_CHECK("csr_fill_kernel");
   }
-  SP_TRY(hipStreamSynchronize(st));
+  HIP_TRY(hipStreamSynchronize(st));
   if (cells && (int64_t)lorder.size() == n) {
     // rows (and columns) renumbered in the locality order: K' = P K P^T
     std::vector<int> inv(n);
@@ -856,31 +822,31 @@ int gpmi_sp_create_matern(int device, const double* points, int64_t n, int d,
     int64_t* dip2 = nullptr;
     int* dix2 = nullptr;
     double* ddv2 = nullptr;
-    SP_TRY(hipMalloc(&sp->perm_d, sizeof(int) * n));
-    SP_TRY(hipMalloc(&dpi, sizeof(int) * n));
-    SP_TRY(hipMalloc(&dip2, sizeof(int64_t) * (n + 1)));
-    SP_TRY(hipMalloc(&dix2, sizeof(int) * std::max<int64_t>(1, sp->nnz)));
-    SP_TRY(hipMalloc(&ddv2, sizeof(double) * std::max<int64_t>(1, sp->nnz)));
-    SP_TRY(hipMemcpyAsync(sp->perm_d, lorder.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-    SP_TRY(hipMemcpyAsync(dpi, inv.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
-    SP_TRY(hipMemcpyAsync(dip2, ip2.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMalloc(&sp->perm_d, sizeof(int) * n));
+    HIP_TRY(hipMalloc(&dpi, sizeof(int) * n));
+    HIP_TRY(hipMalloc(&dip2, sizeof(int64_t) * (n + 1)));
+    HIP_TRY(hipMalloc(&dix2, sizeof(int) * std::max<int64_t>(1, sp->nnz)));
+    HIP_TRY(hipMalloc(&ddv2, sizeof(double) * std::max<int64_t>(1, sp->nnz)));
+    HIP_TRY(hipMemcpyAsync(sp->perm_d, lorder.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dpi, inv.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dip2, ip2.data(), sizeof(int64_t) * (n + 1), hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(csr_permute_kernel, dim3(grid), dim3(256), 0, st, sp->indptr, sp->indices,
                        sp->data, sp->perm_d, dpi, n, dip2, dix2, ddv2);
-    SP_LAUNCH("csr_permute_kernel");
-    SP_TRY(hipStreamSynchronize(st));
-    SP_TRY(hipFree(sp->indptr));
-    SP_TRY(hipFree(sp->indices));
-    SP_TRY(hipFree(sp->data));
-    SP_TRY(hipFree(dpi));
+    LAUNCH_CHECK("csr_permute_kernel");
+    HIP_TRY(hipStreamSynchronize(st));
+    HIP_TRY(hipFree(sp->indptr));
+    HIP_TRY(hipFree(sp->indices));
+    HIP_TRY(hipFree(sp->data));
+    HIP_TRY(hipFree(dpi));
     sp->indptr = dip2;
     sp->indices = dix2;
     sp->data = ddv2;
     sp->perm = std::move(lorder);
   }
-  if (dcell) SP_TRY(hipFree(dcell));
-  SP_TRY(hipFree(dp));
-  SP_TRY(hipFree(ds));
-  SP_TRY(hipFree(dcnt));
+  if (dcell) HIP_TRY(hipFree(dcell));
+  HIP_TRY(hipFree(dp));
+  HIP_TRY(hipFree(ds));
+  HIP_TRY(hipFree(dcnt));
   *out = sp;
   return 0;
 }
@@ -891,7 +857,7 @@ int gpmi_sp_create_dense(gpmi_op* op, gpmi_sp** out) {
   int rc = op_view(op, &v);
   if (rc) return rc;
   if (!v.has_K) return set_error(-1000, "operator has no matrix (load or assemble first)");
-  Guard g(v.device);
+  DeviceGuard g(v.device);
   gpmi_sp* sp = new gpmi_sp();
   sp->device = v.device;
   sp->n = v.n;
@@ -923,7 +889,7 @@ int gpmi_sp_create_dense(gpmi_op* op, gpmi_sp** out) {
 
 int gpmi_sp_destroy(gpmi_sp* sp) {
   if (!sp) return 0;
-  Guard g(sp->device);
+  DeviceGuard g(sp->device);
   if (sp->stream) (void)hipStreamSynchronize(sp->stream);
   if (sp->dYp) (void)hipFree(sp->dYp);
   if (sp->dYp_ms) (void)hipFree(sp->dYp_ms);
@@ -970,11 +936,11 @@ int gpmi_sp_info(const gpmi_sp* sp, int64_t* n, int64_t* nnz) {
 int gpmi_sp_get_csr(gpmi_sp* sp, int64_t* indptr, int* indices, double* data) {
   if (!sp) return set_error(-1006, "null handle");
   if (sp->dK) return set_error(-1105, "a dense operator has no CSR");
-  Guard g(sp->device);
+  DeviceGuard g(sp->device);
   if (sp->perm.empty()) {
-    SP_TRY(hipMemcpy(indptr, sp->indptr, sizeof(int64_t) * (sp->n + 1), hipMemcpyDeviceToHost));
-    SP_TRY(hipMemcpy(indices, sp->indices, sizeof(int) * sp->nnz, hipMemcpyDeviceToHost));
-    SP_TRY(hipMemcpy(data, sp->data, sizeof(double) * sp->nnz, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(indptr, sp->indptr, sizeof(int64_t) * (sp->n + 1), hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(indices, sp->indices, sizeof(int) * sp->nnz, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(data, sp->data, sizeof(double) * sp->nnz, hipMemcpyDeviceToHost));
     return 0;
   }
   // the original order: row i = device row inv[i], columns renamed back and sorted
@@ -982,9 +948,9 @@ int gpmi_sp_get_csr(gpmi_sp* sp, int64_t* indptr, int* indices, double* data) {
   std::vector<int64_t> ip(n + 1);
   std::vector<int> ix(sp->nnz);
   std::vector<double> dv(sp->nnz);
-  SP_TRY(hipMemcpy(ip.data(), sp->indptr, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
-  SP_TRY(hipMemcpy(ix.data(), sp->indices, sizeof(int) * sp->nnz, hipMemcpyDeviceToHost));
-  SP_TRY(hipMemcpy(dv.data(), sp->data, sizeof(double) * sp->nnz, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ip.data(), sp->indptr, sizeof(int64_t) * (n + 1), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(ix.data(), sp->indices, sizeof(int) * sp->nnz, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(dv.data(), sp->data, sizeof(double) * sp->nnz, hipMemcpyDeviceToHost));
   std::vector<int> inv(n);
   for (int64_t r = 0; r < n; ++r) inv[sp->perm[r]] = (int)r;
   indptr[0] = 0;
@@ -1034,12 +1000,12 @@ int sp_scatter_dense(const gpmi_sp* sp, int device, double* K, int64_t ldk, hipS
   if (sp->device != device)
     return set_error(-1011, "sparse and dense operators live on different devices");
   if (sp->dK) return set_error(-1105, "a dense operator has no CSR");
-  SP_TRY(hipStreamSynchronize(sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
   const unsigned grid = (unsigned)((sp->n + 3) / 4);
   hipLaunchKernelGGL(csr_scatter_dense_kernel, dim3(grid), dim3(256), 0, st, sp->indptr,
                      sp->indices, sp->data, sp->perm.empty() ? nullptr : sp->perm_d, sp->n, K,
                      ldk);
-  SP_LAUNCH("csr_scatter_dense_kernel");
+  LAUNCH_CHECK("csr_scatter_dense_kernel");
   return 0;
 }
 
@@ -1050,7 +1016,7 @@ extern "C" {
 int gpmi_sp_spmm(gpmi_sp* sp, double eta, const double* X, int64_t ld, int ncol, double* Y,
                  int64_t ldy) {
   if (!sp) return set_error(-1006, "null handle");
-  Guard g(sp->device);
+  DeviceGuard g(sp->device);
   const int64_t n = sp->n;
   for (int c0 = 0; c0 < ncol; c0 += MAXS) {
     const int s = std::min(MAXS, ncol - c0);
@@ -1059,13 +1025,13 @@ int gpmi_sp_spmm(gpmi_sp* sp, double eta, const double* X, int64_t ld, int ncol,
     std::vector<double> h((size_t)n * s);
     for (int64_t i = 0; i < n; ++i)
       for (int c = 0; c < s; ++c) h[(size_t)i * s + c] = X[orig_row(sp, i) * ld + c0 + c];
-    SP_TRY(hipMemcpyAsync(sp->ws, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice,
+    HIP_TRY(hipMemcpyAsync(sp->ws, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice,
                           sp->stream));
     rc = spmm(sp, sp->ws, sp->ws + n * s, s, eta);
     if (rc) return rc;
-    SP_TRY(hipMemcpyAsync(h.data(), sp->ws + n * s, sizeof(double) * h.size(),
+    HIP_TRY(hipMemcpyAsync(h.data(), sp->ws + n * s, sizeof(double) * h.size(),
                           hipMemcpyDeviceToHost, sp->stream));
-    SP_TRY(hipStreamSynchronize(sp->stream));
+    HIP_TRY(hipStreamSynchronize(sp->stream));
     for (int64_t i = 0; i < n; ++i)
       for (int c = 0; c < s; ++c) Y[orig_row(sp, i) * ldy + c0 + c] = h[(size_t)i * s + c];
   }
@@ -1082,7 +1048,7 @@ int gpmi_sp_lanczos_ex(gpmi_sp* sp, int nprobe, int steps, uint64_t seed, int pr
   if (!sp) return set_error(-1006, "null handle");
   if (steps < 1 || steps > 256 || nprobe < 1)
     return set_error(-1102, "steps must be in [1, 256] and nprobe >= 1");
-  Guard g(sp->device);
+  DeviceGuard g(sp->device);
   const int64_t n = sp->n;
   for (int p0 = 0; p0 < nprobe; p0 += MAXS) {
     const int s = std::min(MAXS, nprobe - p0);
@@ -1095,7 +1061,7 @@ int gpmi_sp_lanczos_ex(gpmi_sp* sp, int nprobe, int steps, uint64_t seed, int pr
       hipLaunchKernelGGL(rademacher_kernel, dim3(grid_ns(n, s)), dim3(256), 0, sp->stream, V, n,
                          s, (unsigned long long)seed, probe_offset + p0,
                          1.0 / std::sqrt((double)n), (const int*)sp->perm_d);
-      SP_LAUNCH("rademacher_kernel");
+      LAUNCH_CHECK("rademacher_kernel");
       return 0;
     };
     if ((rc = probes())) return rc;
@@ -1140,7 +1106,7 @@ int gpmi_sp_lanczos_ex(gpmi_sp* sp, int nprobe, int steps, uint64_t seed, int pr
 int gpmi_sp_cg(gpmi_sp* sp, double eta, const double* rhs, int64_t ld, int nrhs, double rtol,
                int maxiter, double* sol, int64_t ldsol, int* iterations) {
   if (!sp) return set_error(-1006, "null handle");
-  Guard g(sp->device);
+  DeviceGuard g(sp->device);
   const int64_t n = sp->n;
   int max_it_used = 0;
   bool converged = true;
@@ -1166,14 +1132,14 @@ int gpmi_sp_cg(gpmi_sp* sp, double eta, const double* rhs, int64_t ld, int nrhs,
     std::vector<double> h((size_t)ns);
     for (int64_t i = 0; i < n; ++i)
       for (int c = 0; c < s; ++c) h[(size_t)i * s + c] = rhs[orig_row(sp, i) * ld + c0 + c];
-    SP_TRY(hipMemcpyAsync(Rr, h.data(), sizeof(double) * ns, hipMemcpyHostToDevice, sp->stream));
-    SP_TRY(hipMemcpyAsync(Pp, Rr, sizeof(double) * ns, hipMemcpyDeviceToDevice, sp->stream));
-    SP_TRY(hipMemsetAsync(X, 0, sizeof(double) * ns, sp->stream));
+    HIP_TRY(hipMemcpyAsync(Rr, h.data(), sizeof(double) * ns, hipMemcpyHostToDevice, sp->stream));
+    HIP_TRY(hipMemcpyAsync(Pp, Rr, sizeof(double) * ns, hipMemcpyDeviceToDevice, sp->stream));
+    HIP_TRY(hipMemsetAsync(X, 0, sizeof(double) * ns, sp->stream));
     rc = col_dots(sp, Rr, 0, 1, Rr, s, rrb[0]);
     if (rc) return rc;
     hipLaunchKernelGGL(cg_init_kernel, dim3(1), dim3(64), 0, sp->stream, rrb[0], rtol, s, thr,
                        actb[0], err, iters);
-    SP_LAUNCH("cg_init_kernel");
+    LAUNCH_CHECK("cg_init_kernel");
     // The host reads the flags every CG_POLL iterations (one round trip each, not two per
     // iteration): iterations queued after the last column stopped do no vector work.
     constexpr int CG_POLL = 8;
@@ -1187,18 +1153,18 @@ int gpmi_sp_cg(gpmi_sp* sp, double eta, const double* rhs, int64_t ld, int nrhs,
       if (rc) return rc;
       hipLaunchKernelGGL(cg_xr_kernel, dim3(grid), dim3(256), 0, sp->stream, Pp, Q, X, Rr,
                          rrb[cur], pq, actb[cur], n, s, err);   // x += a p, r -= a q
-      SP_LAUNCH("cg_xr_kernel");
+      LAUNCH_CHECK("cg_xr_kernel");
       rc = col_dots(sp, Rr, 0, 1, Rr, s, rrb[cur ^ 1]);
       if (rc) return rc;
       hipLaunchKernelGGL(cg_p_kernel, dim3(grid), dim3(256), 0, sp->stream, Rr, Pp, rrb[cur],
                          rrb[cur ^ 1], actb[cur], actb[cur ^ 1], thr, it, iters, n, s);
-      SP_LAUNCH("cg_p_kernel");   // p = r + b p
+      LAUNCH_CHECK("cg_p_kernel");   // p = r + b p
       if ((it + 1) % CG_POLL == 0 || it + 1 == maxiter) {
-        SP_TRY(hipMemcpyAsync(flags.data(), actb[cur ^ 1], sizeof(int) * s, hipMemcpyDeviceToHost,
+        HIP_TRY(hipMemcpyAsync(flags.data(), actb[cur ^ 1], sizeof(int) * s, hipMemcpyDeviceToHost,
                               sp->stream));
-        SP_TRY(hipMemcpyAsync(flags.data() + MAXS, err, sizeof(int), hipMemcpyDeviceToHost,
+        HIP_TRY(hipMemcpyAsync(flags.data() + MAXS, err, sizeof(int), hipMemcpyDeviceToHost,
                               sp->stream));
-        SP_TRY(hipStreamSynchronize(sp->stream));
+        HIP_TRY(hipStreamSynchronize(sp->stream));
         if (flags[MAXS])
           return set_error(1, "CG: p^T (K + eta I) p <= 0 (K + eta I is not positive definite)");
         bool any = false;
@@ -1209,21 +1175,21 @@ int gpmi_sp_cg(gpmi_sp* sp, double eta, const double* rhs, int64_t ld, int nrhs,
     // the residual norms after the last iteration that ran sit in rrb[it_used & 1] (rrb[0]
     // when none ran); the no-op iterations queued after it rewrite the same values
     std::vector<double> rr(s), bnt(s);
-    SP_TRY(hipMemcpyAsync(flags.data() + MAXS, err, sizeof(int) * 2, hipMemcpyDeviceToHost,
+    HIP_TRY(hipMemcpyAsync(flags.data() + MAXS, err, sizeof(int) * 2, hipMemcpyDeviceToHost,
                           sp->stream));
-    SP_TRY(hipStreamSynchronize(sp->stream));
+    HIP_TRY(hipStreamSynchronize(sp->stream));
     if (flags[MAXS])
       return set_error(1, "CG: p^T (K + eta I) p <= 0 (K + eta I is not positive definite)");
     const int it_used = flags[MAXS + 1];
     max_it_used = std::max(max_it_used, it_used);
-    SP_TRY(hipMemcpyAsync(bnt.data(), thr, sizeof(double) * s, hipMemcpyDeviceToHost, sp->stream));
-    SP_TRY(hipMemcpyAsync(rr.data(), rrb[it_used & 1], sizeof(double) * s, hipMemcpyDeviceToHost,
+    HIP_TRY(hipMemcpyAsync(bnt.data(), thr, sizeof(double) * s, hipMemcpyDeviceToHost, sp->stream));
+    HIP_TRY(hipMemcpyAsync(rr.data(), rrb[it_used & 1], sizeof(double) * s, hipMemcpyDeviceToHost,
                           sp->stream));
-    SP_TRY(hipStreamSynchronize(sp->stream));
+    HIP_TRY(hipStreamSynchronize(sp->stream));
     for (int c = 0; c < s; ++c)
       if (!(std::sqrt(rr[c]) <= bnt[c])) converged = false;
-    SP_TRY(hipMemcpyAsync(h.data(), X, sizeof(double) * ns, hipMemcpyDeviceToHost, sp->stream));
-    SP_TRY(hipStreamSynchronize(sp->stream));
+    HIP_TRY(hipMemcpyAsync(h.data(), X, sizeof(double) * ns, hipMemcpyDeviceToHost, sp->stream));
+    HIP_TRY(hipStreamSynchronize(sp->stream));
     for (int64_t i = 0; i < n; ++i)
       for (int c = 0; c < s; ++c) sol[orig_row(sp, i) * ldsol + c0 + c] = h[(size_t)i * s + c];
   }
@@ -1313,11 +1279,11 @@ struct MsDev {
 
   MsPin* pin() { return pin_host; }
   int mark(int slot) {
-    SP_TRY(hipEventRecord(sp->ms_ev[slot], str));
+    HIP_TRY(hipEventRecord(sp->ms_ev[slot], str));
     return 0;
   }
   int wait(int slot) {
-    SP_TRY(hipEventSynchronize(sp->ms_ev[slot]));
+    HIP_TRY(hipEventSynchronize(sp->ms_ev[slot]));
     return 0;
   }
 
@@ -1329,18 +1295,18 @@ struct MsDev {
     if (rows == 0) {
       hipLaunchKernelGGL(ms_dots2_kernel, dim3(MS_DOT_BLK), dim3(256), 0, str,
                          (const double*)blk.R, (const double*)blk.W, n, s, spart);
-      SP_LAUNCH("ms_dots2_kernel");
+      LAUNCH_CHECK("ms_dots2_kernel");
       rows = MS_DOT_BLK;
     }
     hipLaunchKernelGGL(ms_cg2_reduce_kernel, dim3(2 * s + neb), dim3(256), 0, str,
                        (const double*)spart, rows, s, (const double*)blk.bpart, MS_UB, neb, dred);
-    SP_LAUNCH("ms_cg2_reduce_kernel");
+    LAUNCH_CHECK("ms_cg2_reduce_kernel");
     hipLaunchKernelGGL(ms_cg2_update_kernel, dim3(MS_UB + 1), dim3(256), 0, str,
                        (const double*)Bd, blk.R, (const double*)blk.W, blk.S, blk.sc[k & 1],
                        blk.sc[(k + 1) & 1], blk.sh, (const double*)dred, blk.bpart,
                        (const double*)dshift, S, s, nbd, rtol * rtol, k, n,
                        slot >= 0 ? pin_dev + slot : (MsPin*)nullptr);
-    SP_LAUNCH("ms_cg2_update_kernel");
+    LAUNCH_CHECK("ms_cg2_update_kernel");
     return 0;
   }
 
@@ -1391,7 +1357,7 @@ struct MsDev {
       most = std::max<int64_t>(most, A.job[q].rows * a * A.job[q].L);
     const unsigned gx = (unsigned)std::max<int64_t>(1, std::min<int64_t>(1024, (most + 255) / 256));
     hipLaunchKernelGGL(ms_compact_kernel, dim3(gx, A.njob + 1), dim3(256), 0, str, A);
-    SP_LAUNCH("ms_compact_kernel");
+    LAUNCH_CHECK("ms_compact_kernel");
     blk = nw;
     buf = nbuf;
     return 0;
@@ -1429,14 +1395,14 @@ static int ms_alloc(MsDev& d, int s, int nrhs, int kind, bool gfin) {
     if (int rc = grow(&sp->ms_gfin, &sp->ms_gfin_doubles, (size_t)S * nbd * s)) return rc;
   if (!sp->ms_pin) {
     // coherent: the batch's last update kernel stores the end state into it directly
-    SP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sp->ms_pin), 2 * sizeof(MsPin),
+    HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&sp->ms_pin), 2 * sizeof(MsPin),
                          hipHostMallocCoherent | hipHostMallocMapped));
     for (hipEvent_t* e : {&sp->ms_ev[0], &sp->ms_ev[1]})
-      SP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
+      HIP_TRY(hipEventCreateWithFlags(e, hipEventDisableTiming));
   }
   d.pin_host = reinterpret_cast<MsPin*>(sp->ms_pin);
   d.pin_dev = nullptr;
-  SP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&d.pin_dev), sp->ms_pin, 0));
+  HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&d.pin_dev), sp->ms_pin, 0));
   return 0;
 }
 
@@ -1453,34 +1419,34 @@ static int ms_start(MsDev& d, const double* etas, const double* rhs, int64_t ld,
   if (!rhs) {
     Hsrc = sp->rhs_dev;
   } else if (ld == nrhs) {
-    SP_TRY(hipMemcpyAsync(d.Hs, rhs, sizeof(double) * n * nrhs, hipMemcpyHostToDevice, str));
+    HIP_TRY(hipMemcpyAsync(d.Hs, rhs, sizeof(double) * n * nrhs, hipMemcpyHostToDevice, str));
   } else {
     std::vector<double> h((size_t)n * nrhs);
     for (int64_t i = 0; i < n; ++i)
       for (int c = 0; c < nrhs; ++c) h[(size_t)i * nrhs + c] = rhs[i * ld + c];
-    SP_TRY(hipMemcpyAsync(d.Hs, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, str));
-    SP_TRY(hipStreamSynchronize(str));
+    HIP_TRY(hipMemcpyAsync(d.Hs, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, str));
+    HIP_TRY(hipStreamSynchronize(str));
   }
   hipLaunchKernelGGL(rows_gather_kernel, dim3(grid_ns(n, nbd)), dim3(256), 0, str, Hsrc, nrhs,
                      (const int*)sp->perm_d, n, nbd, d.Bd);
-  SP_LAUNCH("rows_gather_kernel");
+  LAUNCH_CHECK("rows_gather_kernel");
   std::vector<double> hd(S);
   for (int j = 0; j < S; ++j) hd[j] = etas[j] - d.eta0;
-  SP_TRY(hipMemcpyAsync(d.dshift, hd.data(), sizeof(double) * S, hipMemcpyHostToDevice, str));
+  HIP_TRY(hipMemcpyAsync(d.dshift, hd.data(), sizeof(double) * S, hipMemcpyHostToDevice, str));
   if (full) {
-    SP_TRY(hipMemcpyAsync(d.blk.R, d.Bd, sizeof(double) * ns, hipMemcpyDeviceToDevice, str));
+    HIP_TRY(hipMemcpyAsync(d.blk.R, d.Bd, sizeof(double) * ns, hipMemcpyDeviceToDevice, str));
   } else {
     hipLaunchKernelGGL(rows_gather_kernel, dim3(grid_ns(n, s)), dim3(256), 0, str, d.Bd + c_lo,
                        nbd, (const int*)nullptr, n, s, d.blk.R);
-    SP_LAUNCH("rows_gather_kernel");
+    LAUNCH_CHECK("rows_gather_kernel");
   }
   // s_{-1} = 0 (beta_{-1} = 0 multiplies it: no NaN may stand there)
-  SP_TRY(hipMemsetAsync(d.blk.S, 0, sizeof(double) * ns, str));
+  HIP_TRY(hipMemsetAsync(d.blk.S, 0, sizeof(double) * ns, str));
   launch_ms_dots(d.Bd, d.blk.R, n, s, d.ipart, MS_NBLK, str, nbd);
-  SP_LAUNCH("ms_dots_partial_kernel");
+  LAUNCH_CHECK("ms_dots_partial_kernel");
   hipLaunchKernelGGL(ms_init_kernel, dim3(1), dim3(1024), 0, str, d.blk.sc[0], d.blk.sh,
                      (const double*)d.ipart, MS_NBLK, S, s, nbd, d.pin_dev);
-  SP_LAUNCH("ms_init_kernel");
+  LAUNCH_CHECK("ms_init_kernel");
   return 0;
 }
 
@@ -1496,21 +1462,21 @@ static int ms_finish(MsDev& d, const MsRun& run, int nrhs, int nsub, bool trace,
   const MsShift& sh = d.blk.sh;
   hipLaunchKernelGGL(ms_cg2_close_kernel, dim3(1), dim3(256), 0, str, cur, sh,
                      (const double*)d.dshift, S, s, nbd);
-  SP_LAUNCH("ms_cg2_close_kernel");
+  LAUNCH_CHECK("ms_cg2_close_kernel");
   int flag = 0, it_stop = -1;
   std::vector<int> hact(s);
-  SP_TRY(hipMemcpyAsync(hact.data(), cur.active, sizeof(int) * s, hipMemcpyDeviceToHost, str));
-  SP_TRY(hipMemcpyAsync(&flag, sh.flags, sizeof(int), hipMemcpyDeviceToHost, str));
-  SP_TRY(hipMemcpyAsync(&it_stop, sh.it_stop, sizeof(int), hipMemcpyDeviceToHost, str));
+  HIP_TRY(hipMemcpyAsync(hact.data(), cur.active, sizeof(int) * s, hipMemcpyDeviceToHost, str));
+  HIP_TRY(hipMemcpyAsync(&flag, sh.flags, sizeof(int), hipMemcpyDeviceToHost, str));
+  HIP_TRY(hipMemcpyAsync(&it_stop, sh.it_stop, sizeof(int), hipMemcpyDeviceToHost, str));
   std::vector<double> hg((size_t)S * nbd * s);
-  SP_TRY(hipMemcpyAsync(hg.data(), sh.g, sizeof(double) * hg.size(), hipMemcpyDeviceToHost, str));
+  HIP_TRY(hipMemcpyAsync(hg.data(), sh.g, sizeof(double) * hg.size(), hipMemcpyDeviceToHost, str));
   std::vector<double> g_final;   // [j][cp][c original], the dropped columns' entries
   if (run.compactions > 0) {
     g_final.resize((size_t)S * nbd * s0);
-    SP_TRY(hipMemcpyAsync(g_final.data(), sp->ms_gfin, sizeof(double) * g_final.size(),
+    HIP_TRY(hipMemcpyAsync(g_final.data(), sp->ms_gfin, sizeof(double) * g_final.size(),
                           hipMemcpyDeviceToHost, str));
   }
-  SP_TRY(hipStreamSynchronize(str));
+  HIP_TRY(hipStreamSynchronize(str));
   sp->last_compactions = run.compactions;
   sp->last_segments = run.segments;
   if (flag)
@@ -1538,7 +1504,7 @@ static int msgram_cg2(gpmi_sp* sp, const double* etas, int neta, const double* r
                       double* G, int* iterations) {
   const int nsub = c_hi - c_lo;
   const bool full = nsub == nrhs;
-  Guard g(sp->device);
+  DeviceGuard g(sp->device);
   int s = nsub;
   int kind = 0;
   if (int rc = spmm_kind(sp, s, &kind)) return rc;
@@ -1554,7 +1520,7 @@ static int msgram_cg2(gpmi_sp* sp, const double* etas, int neta, const double* r
     // ms alone) plus its host-side quadrature became the step's tail: round 6 alternating
     // runs, high / normal / low: cfg 5 9.80-9.92 / 9.40-9.44 / 9.77-10.05 ms, cfg 4
     // 2.86-2.90 / 2.80-2.82 / 2.83-2.86 ms.
-    SP_TRY(hipStreamCreateWithFlags(&sp->ms_stream, hipStreamNonBlocking));
+    HIP_TRY(hipStreamCreateWithFlags(&sp->ms_stream, hipStreamNonBlocking));
   }
   // GPMI_MS_COMPACT=0: no active-column compaction
   const char* cenv = std::getenv("GPMI_MS_COMPACT");
@@ -1576,7 +1542,7 @@ static int msgram_cg2(gpmi_sp* sp, const double* etas, int neta, const double* r
   MsRun run;
   const int rc = ms_schedule(dev, s, rtol, maxiter, compact_on, trace, &run);
   if (run.indefinite) {
-    SP_TRY(hipStreamSynchronize(dev.str));
+    HIP_TRY(hipStreamSynchronize(dev.str));
     return set_error(1, "multi-shift CG: p^T (K + min(eta) I) p <= 0 (not positive definite)");
   }
   if (rc) return rc;
@@ -1616,28 +1582,28 @@ int gpmi_sp_set_rhs(gpmi_sp* sp, const double* rhs, int64_t ld, int nrhs) {
   if (!sp) return set_error(-1006, "null handle");
   if (!rhs || nrhs < 1 || nrhs > MS_MAXS || ld < nrhs)
     return set_error(-1104, "set_rhs: need 1 <= nrhs <= 16 and ld >= nrhs");
-  Guard g(sp->device);
+  DeviceGuard g(sp->device);
   const int64_t n = sp->n;
   if (sp->rhs_dev && sp->rhs_nrhs != nrhs) {
-    SP_TRY(hipFree(sp->rhs_dev));
+    HIP_TRY(hipFree(sp->rhs_dev));
     sp->rhs_dev = nullptr;
   }
-  if (!sp->rhs_dev) SP_TRY(hipMalloc(&sp->rhs_dev, sizeof(double) * (size_t)n * nrhs));
+  if (!sp->rhs_dev) HIP_TRY(hipMalloc(&sp->rhs_dev, sizeof(double) * (size_t)n * nrhs));
   sp->rhs_nrhs = nrhs;
   if (ld == nrhs) {
-    SP_TRY(hipMemcpy(sp->rhs_dev, rhs, sizeof(double) * (size_t)n * nrhs, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sp->rhs_dev, rhs, sizeof(double) * (size_t)n * nrhs, hipMemcpyHostToDevice));
   } else {
     std::vector<double> h((size_t)n * nrhs);
     for (int64_t i = 0; i < n; ++i)
       for (int c = 0; c < nrhs; ++c) h[(size_t)i * nrhs + c] = rhs[i * ld + c];
-    SP_TRY(hipMemcpy(sp->rhs_dev, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(sp->rhs_dev, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice));
   }
   return 0;
 }
 
 int gpmi_sp_spmm_info(gpmi_sp* sp, int* windowed, double* mean_window, int* max_window) {
   if (!sp) return set_error(-1006, "null handle");
-  Guard g(sp->device);
+  DeviceGuard g(sp->device);
   if (sp->dK) {   // dense: no window
     if (windowed) *windowed = 0;
     if (mean_window) *mean_window = 0.0;
@@ -1655,7 +1621,7 @@ int gpmi_sp_spmm_info(gpmi_sp* sp, int* windowed, double* mean_window, int* max_
 
 int gpmi_sp_spmm_kernel(gpmi_sp* sp, int s, int* kind) {
   if (!sp || !kind) return set_error(-1006, "null handle");
-  Guard g(sp->device);
+  DeviceGuard g(sp->device);
   return spmm_kind(sp, s, kind);
 }
 
@@ -1737,23 +1703,23 @@ extern "C" {
 
 int gpmi_sp_set_timing(gpmi_sp* sp, int enable) {
   if (!sp) return set_error(-1006, "null handle");
-  Guard g(sp->device);
+  DeviceGuard g(sp->device);
   std::lock_guard<std::mutex> lock(sp->timing_mu);
   if (enable && !sp->stamps && !sp->dK) {
     if (int rc = ensure_window(sp)) return rc;
     const size_t per = sizeof(unsigned long long) * 2 * (size_t)std::max<int64_t>(1, sp->win_nblk);
     sp->stamp_cap = (int)std::min<size_t>(STAMP_CAP, STAMP_BYTES / per);
-    SP_TRY(hipMalloc(&sp->stamps, per * sp->stamp_cap));
-    SP_TRY(hipDeviceGetAttribute(&sp->wall_khz, hipDeviceAttributeWallClockRate, sp->device));
+    HIP_TRY(hipMalloc(&sp->stamps, per * sp->stamp_cap));
+    HIP_TRY(hipDeviceGetAttribute(&sp->wall_khz, hipDeviceAttributeWallClockRate, sp->device));
   }
   hipLaunchKernelGGL(gpmi::timing_mark_kernel, dim3(1), dim3(64), 0, sp->stream, enable);
-  SP_LAUNCH("timing_mark_kernel");
+  LAUNCH_CHECK("timing_mark_kernel");
   if (enable) {
     // the pairs of an earlier window go back to the pool (their streams are idle
     // once the caller synchronised; wait for them anyway)
     for (auto& r : sp->spmm_log) {
       if (r.slot >= 0) continue;
-      SP_TRY(hipEventSynchronize(r.e1));
+      HIP_TRY(hipEventSynchronize(r.e1));
       sp->ev_pool.push_back(r.e0);
       sp->ev_pool.push_back(r.e1);
     }
@@ -1768,23 +1734,23 @@ int gpmi_sp_set_timing(gpmi_sp* sp, int enable) {
 int gpmi_sp_spmm_timing(gpmi_sp* sp, int max_widths, int* n_widths, int* widths, int* launches,
                         double* total_ms) {
   if (!sp || !n_widths) return set_error(-1006, "null handle");
-  Guard g(sp->device);
+  DeviceGuard g(sp->device);
   std::lock_guard<std::mutex> lock(sp->timing_mu);
   std::map<int, std::pair<int, double>> acc;
   std::vector<unsigned long long> st;
   if (sp->stamps_used > 0) {
     // every stamped launch's span, reduced on the device (after the logged work)
-    SP_TRY(hipDeviceSynchronize());
+    HIP_TRY(hipDeviceSynchronize());
     unsigned long long* span = nullptr;
-    SP_TRY(hipMalloc(&span, sizeof(unsigned long long) * 2 * sp->stamps_used));
+    HIP_TRY(hipMalloc(&span, sizeof(unsigned long long) * 2 * sp->stamps_used));
     hipLaunchKernelGGL(gpmi::stamp_span_kernel, dim3(sp->stamps_used), dim3(256), 0, sp->stream,
                        sp->stamps, sp->win_nblk, span);
-    SP_LAUNCH("stamp_span_kernel");
+    LAUNCH_CHECK("stamp_span_kernel");
     st.resize((size_t)2 * sp->stamps_used);
-    SP_TRY(hipMemcpyAsync(st.data(), span, sizeof(unsigned long long) * st.size(),
+    HIP_TRY(hipMemcpyAsync(st.data(), span, sizeof(unsigned long long) * st.size(),
                           hipMemcpyDeviceToHost, sp->stream));
-    SP_TRY(hipStreamSynchronize(sp->stream));
-    SP_TRY(hipFree(span));
+    HIP_TRY(hipStreamSynchronize(sp->stream));
+    HIP_TRY(hipFree(span));
   }
   for (auto& r : sp->spmm_log) {
     double ms = 0.0;
@@ -1793,9 +1759,9 @@ int gpmi_sp_spmm_timing(gpmi_sp* sp, int max_widths, int* n_widths, int* widths,
       if (t1 < t0 || sp->wall_khz <= 0) return set_error(-1107, "SpMM timing: a stamp slot was not written");
       ms = (double)(t1 - t0) / (double)sp->wall_khz;
     } else {
-      SP_TRY(hipEventSynchronize(r.e1));
+      HIP_TRY(hipEventSynchronize(r.e1));
       float fms = 0.f;
-      SP_TRY(hipEventElapsedTime(&fms, r.e0, r.e1));
+      HIP_TRY(hipEventElapsedTime(&fms, r.e0, r.e1));
       ms = fms;
     }
     auto& a = acc[r.s];
@@ -1817,16 +1783,16 @@ int gpmi_sp_spmm_timing(gpmi_sp* sp, int max_widths, int* n_widths, int* widths,
 int gpmi_sp_bench_spmm(gpmi_sp* sp, int s, int reps, double eta, double* avg_ms) {
   if (!sp) return set_error(-1006, "null handle");
   if (s < 1 || s > 64 || reps < 1) return set_error(-1103, "s in [1, 64], reps >= 1");
-  Guard g(sp->device);
+  DeviceGuard g(sp->device);
   const int64_t ns = sp->n * s;
   int rc = grow(&sp->ws, &sp->ws_doubles, (size_t)2 * ns);
   if (rc) return rc;
   hipLaunchKernelGGL(rademacher_kernel, dim3(grid_ns(sp->n, s)), dim3(256), 0, sp->stream, sp->ws,
                      sp->n, s, 12345ull, 0, 1.0, (const int*)nullptr);
-  SP_LAUNCH("rademacher_kernel");
+  LAUNCH_CHECK("rademacher_kernel");
   hipEvent_t e0, e1;
-  SP_TRY(hipEventCreate(&e0));
-  SP_TRY(hipEventCreate(&e1));
+  HIP_TRY(hipEventCreate(&e0));
+  HIP_TRY(hipEventCreate(&e1));
   // warm-up, kept out of the in-step timing log (a logged warm-up made
   // the log 51 spans for the 50 timed launches, mixing a cold launch into the mean
   // span the bench subtracts from the gated period)
@@ -1844,14 +1810,14 @@ int gpmi_sp_bench_spmm(gpmi_sp* sp, int s, int reps, double eta, double* avg_ms)
   if (rc) return rc;
   // the timed launches wait behind a gate until all of them are queued (at most 2 s)
   int* flag = nullptr;
-  SP_TRY(hipHostMalloc(&flag, sizeof(int), hipHostMallocCoherent));
+  HIP_TRY(hipHostMalloc(&flag, sizeof(int), hipHostMallocCoherent));
   *flag = 0;
   int khz = 0;
-  SP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, sp->device));
+  HIP_TRY(hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, sp->device));
   hipLaunchKernelGGL(gpmi::gate_kernel, dim3(1), dim3(64), 0, sp->stream, flag,
                      (unsigned long long)std::max(khz, 1) * 2000ull);
-  SP_LAUNCH("gate_kernel");
-  SP_TRY(hipEventRecord(e0, sp->stream));
+  LAUNCH_CHECK("gate_kernel");
+  HIP_TRY(hipEventRecord(e0, sp->stream));
   for (int r = 0; r < reps && rc == 0; ++r) rc = spmm(sp, sp->ws, sp->ws + ns, s, eta);
   __atomic_store_n(flag, 1, __ATOMIC_SEQ_CST);
   if (rc) {
@@ -1859,14 +1825,14 @@ int gpmi_sp_bench_spmm(gpmi_sp* sp, int s, int reps, double eta, double* avg_ms)
     (void)hipHostFree(flag);
     return rc;
   }
-  SP_TRY(hipEventRecord(e1, sp->stream));
-  SP_TRY(hipEventSynchronize(e1));
-  SP_TRY(hipHostFree(flag));
+  HIP_TRY(hipEventRecord(e1, sp->stream));
+  HIP_TRY(hipEventSynchronize(e1));
+  HIP_TRY(hipHostFree(flag));
   float ms = 0.f;
-  SP_TRY(hipEventElapsedTime(&ms, e0, e1));
+  HIP_TRY(hipEventElapsedTime(&ms, e0, e1));
   *avg_ms = ms / reps;
-  SP_TRY(hipEventDestroy(e0));
-  SP_TRY(hipEventDestroy(e1));
+  HIP_TRY(hipEventDestroy(e0));
+  HIP_TRY(hipEventDestroy(e1));
   return 0;
 }
 

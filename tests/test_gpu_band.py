@@ -688,3 +688,93 @@ def test_band_selected_inversion_traceinv_exponent_2(gp, n):
     assert rel(ld, ld0) < 1e-13 and rel(G2, G20) < 1e-12 and rel(G3, G30) < 1e-12
     assert rel(op.traceinv(0.05, 2), ex2[1]) < 1e-10
     assert op._eig is None
+
+
+def _band_with_rhs(K, X, z):
+    band = _mc(K).band()
+    band.set_rhs(numpy.column_stack([X, z]))
+    return band
+
+
+def _raw_traces(band, etas, ex2, want_tr1=True):
+    """gpmi_band_der_terms_ex2 (ex2) or gpmi_band_traceinv2 with tr2 requested, called
+    through the library directly: Band.der_terms / Band.traceinv split the etas into
+    TR_CHUNK = 64 first, so the library's own chunking is not reached through them.
+    -> (rc, dict of the output arrays)"""
+    from gaussian_proc import _hip
+    e = _hip.as_c(numpy.asarray(etas, dtype=float))
+    k, m = e.shape[0], band.nrhs
+    o = {'tr1': numpy.empty(k), 'tr2': numpy.empty(k), 'info': numpy.zeros(k, dtype=numpy.int32)}
+    info = o['info'].ctypes.data_as(_hip.c_int_p)
+    tr1 = _hip.dptr(o['tr1']) if want_tr1 else None
+    if ex2:
+        o.update(ld=numpy.empty(k), g1=numpy.empty((k, m, m)), g2=numpy.empty((k, m, m)),
+                 g3=numpy.empty((k, m, m)))
+        rc = band.lib.gpmi_band_der_terms_ex2(band.h, _hip.dptr(e), k, _hip.dptr(o['ld']),
+                                              _hip.dptr(o['g1']), _hip.dptr(o['g2']),
+                                              _hip.dptr(o['g3']), tr1, _hip.dptr(o['tr2']), info)
+    else:
+        rc = band.lib.gpmi_band_traceinv2(band.h, _hip.dptr(e), k, tr1, _hip.dptr(o['tr2']), info)
+    return rc, o
+
+
+@pytest.mark.parametrize('n', [129, 300])
+def test_band_library_chunks_past_tan_max(gp, n):
+    """130 etas with tr2 in one library call (gpmi_band_traceinv2, gpmi_band_der_terms_ex2:
+    the tangent store holds GPMI_BAND_TAN_MAX = 64 etas, so chunks of 64, 64 and 2)
+    equal three direct calls with those etas exactly (the same launches on the same
+    data), and one-eta calls to the tolerances of
+    test_band_selected_inversion_traceinv_exponent_2 between two device paths (traces
+    and Gram blocks 1e-12, logdet 1e-13). n = 129 and 300: two and three blocks, one
+    level and an odd level size. Past GPMI_BAND_DER_MAX etas: -1203; traceinv2 without
+    tr1: -1006."""
+    K, X, z = _inputs(n, n + 23, nu=2.5, scale=0.15)
+    band = _band_with_rhs(K, X, z)
+    etas = numpy.logspace(-2, 1.5, 130)
+    for ex2 in (False, True):
+        rc, full = _raw_traces(band, etas, ex2)
+        assert rc == 0
+        assert not numpy.any(full['info'])
+        parts = []
+        for lo, hi in ((0, 64), (64, 128), (128, 130)):
+            rc, part = _raw_traces(band, etas[lo:hi], ex2)
+            assert rc == 0
+            parts.append(part)
+        for key, val in full.items():
+            numpy.testing.assert_array_equal(val, numpy.concatenate([p[key] for p in parts]),
+                                             err_msg=key)
+        ones = [_raw_traces(band, etas[i:i + 1], ex2) for i in range(130)]
+        assert not any(rc for rc, _ in ones)
+        for key, val in full.items():
+            one = numpy.concatenate([o[key] for _, o in ones])
+            if key == 'info':
+                numpy.testing.assert_array_equal(val, one)
+            else:
+                assert rel(val, one) < (1e-13 if key == 'ld' else 1e-12), (ex2, key)
+        rc, _ = _raw_traces(band, numpy.logspace(-2, 1.5, 257), ex2)
+        assert rc == -1203
+    rc, _ = _raw_traces(band, etas[:3], False, want_tr1=False)
+    assert rc == -1006
+
+
+@pytest.mark.parametrize('n', [129, 300])
+def test_band_capacity_groups_regrow_independently(gp, n):
+    """One handle through loglik with 3, 70 and 3 etas, then der_terms with both traces
+    on 2 and on 5 etas: the io, cyclic-reduction, selected-inversion, tangent and
+    derivative groups grow at different calls (70 etas take the sequential kernel, so
+    only io grows there), and a capacity left larger than a call needs does no harm.
+    Every result equals that of a fresh handle making the same call alone."""
+    K, X, z = _inputs(n, n + 29, nu=2.5, scale=0.15)
+    band = _band_with_rhs(K, X, z)
+    rng = numpy.random.RandomState(n)
+    for call, neta in (('loglik', 3), ('loglik', 70), ('loglik', 3), ('der', 2), ('der', 5)):
+        etas = 10.0 ** rng.uniform(-2, 1.5, neta)
+        fresh = _band_with_rhs(K, X, z)
+        if call == 'loglik':
+            got, ref = band.loglik(etas), fresh.loglik(etas)
+        else:
+            got, ref = band.der_terms(etas, traceinv=2), fresh.der_terms(etas, traceinv=2)
+        assert len(got) == len(ref)
+        for a, b in zip(got, ref):
+            numpy.testing.assert_array_equal(a, b, err_msg='%s %d' % (call, neta))
+        fresh.close()

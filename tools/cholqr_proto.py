@@ -15,7 +15,7 @@ from band_proto import v_of, t_of, householder_panel  # noqa: E402
 U_RND = 2.0 ** -53
 
 
-FO_TAU = (0.0, 1e-4, 3e-8)   # first-order thresholds on ||G - I||_F (gpmi_band_api.hip)
+FO_TAU = (0.0, 1e-4, 3e-8)   # first-order thresholds on ||G - I||_F (gpmi_band_host.h: BandReduce::cq_fo)
 
 
 def cholqr_panel(P, shifted_passes=1, passes=3, first_order=True):
