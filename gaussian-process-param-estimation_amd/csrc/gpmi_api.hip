@@ -20,6 +20,7 @@
 #include "gpmi_internal.h"
 #include "gpmi_host.h"
 #include "gpmi_band.h"
+#include "gpmi_dense_plan.h"
 #include "../../include/gpmi.h"
 
 using namespace gpmi;
@@ -48,6 +49,7 @@ struct gpmi_op {
   int nt = 0;
   int max_batch = 1;
   int outer = 16;                      // outer panel width in 128-column tiles
+  int panel_mode = DENSE_REC;          // schedule inside an outer panel (GPMI_PANEL)
   hipStream_t stream = nullptr;
   hipStream_t stream3 = nullptr;       // second batch group (groups == 2)
   int groups = 0;                      // 2: the batch runs as two halves on two streams;
@@ -97,6 +99,9 @@ struct gpmi_op {
   std::vector<std::pair<int, double>> syrk_log;  // (event index, flops)
   std::vector<std::array<int, 3>> syrk_shape;    // (w, t, kdim) per logged launch
   double last_syrk_busy_ms = 0.0;                // union of syrk launch intervals
+  bool trace = false;                            // GPMI_SYRK_TRACE: per-class breakdown
+  std::vector<hipEvent_t> colpanel_ev;           // (begin, end) per colpanel_kernel launch
+  size_t colpanel_ev_used = 0;
 
   BatchPtrs ptrs() const {
     BatchPtrs p;
@@ -177,37 +182,48 @@ int launch_syrk(gpmi_op* op, hipStream_t st, int b0, int nb, int tc0, int w, int
   return 0;
 }
 
-// Recursive panel factorization of tile columns [c0, c0 + W) (all contributions
-// of columns < c0 already applied): factor the left half, update the right half
-// from it (a band SYRK with kdim = half width), factor the right half. A single
-// column is the diagonal-block kernel (Cholesky, inverse, fused forward solve,
-// logdet / Gram partials) followed by the panel kernel (L_ik and r_i updates).
-int factor_panel(gpmi_op* op, const BatchPtrs& P, int b0, int nb, hipStream_t st, int c0,
-                 int W) {
-  const int nt = op->nt;
-  if (W == 1) {
-    if (op->dry) return 0;
-    hipLaunchKernelGGL(diag_block_kernel, dim3(nb), dim3(256), 0, st, P, (int64_t)op->n_pad,
-                       c0, nt);
+// One launch of an outer panel's factorization (gpmi_dense_plan.h): the diagonal-block
+// kernel of a column (Cholesky, inverse, fused forward solve, logdet / Gram partials),
+// then either the left-looking column kernel (column update, L_ik and r_i updates, next
+// diagonal tile) or, in the recursive schedule, the panel kernel (L_ik and r_i updates).
+int factor_panel(gpmi_op* op, const BatchPtrs& P, int nb, hipStream_t st,
+                 const DenseLaunch& L) {
+  if (op->dry) return 0;
+  const int64_t lda = op->n_pad;
+  if (L.kind == DENSE_DIAG) {
+    hipLaunchKernelGGL(diag_block_kernel, dim3(nb), dim3(256), 0, st, P, lda, L.col, op->nt);
     LAUNCH_CHECK("diag_block_kernel");
-    if (c0 + 1 < nt) {
-      hipLaunchKernelGGL(panel_kernel, dim3(nt - c0 - 1, nb), dim3(256), 0, st, P,
-                         (int64_t)op->n_pad, c0);
-      LAUNCH_CHECK("panel_kernel");
+  } else if (L.kind == DENSE_PANEL) {
+    hipLaunchKernelGGL(panel_kernel, dim3(L.r1 - L.r0, nb), dim3(256), 0, st, P, lda, L.col);
+    LAUNCH_CHECK("panel_kernel");
+  } else {
+    // (its events only under GPMI_SYRK_TRACE: the default timed run records none here)
+    const bool ev = op->timing && op->trace;
+    size_t evi = op->colpanel_ev_used;
+    if (ev) {
+      while (op->colpanel_ev.size() < evi + 2) {
+        hipEvent_t e;
+        HIP_TRY(hipEventCreateWithFlags(&e, timing_event_flags()));
+        op->colpanel_ev.push_back(e);
+      }
+      HIP_TRY(hipEventRecord(op->colpanel_ev[evi], st));
     }
-    return 0;
+    // block 0 is row tile col + 1, the one that goes on to the next diagonal tile
+    hipLaunchKernelGGL(colpanel_kernel, dim3(L.r1 - L.r0, nb), dim3(256), 0, st, P, lda, L.col,
+                       L.p0 / TS, L.next_diag ? 1 : 0);
+    LAUNCH_CHECK("colpanel_kernel");
+    if (ev) {
+      HIP_TRY(hipEventRecord(op->colpanel_ev[evi + 1], st));
+      op->colpanel_ev_used = evi + 2;
+    }
   }
-  const int h = W / 2;
-  int rc = factor_panel(op, P, b0, nb, st, c0, h);
-  if (rc) return rc;
-  rc = launch_syrk(op, st, b0, nb, c0 + h, W - h, nt - c0 - h, c0 * TS, h * TS);
-  if (rc) return rc;
-  return factor_panel(op, P, b0, nb, st, c0 + h, W - h);
+  return 0;
 }
 
 
 // The blocked factorization schedule over outer panels P_k of `outer` tile
-// columns, in order on one stream: factor P_k (recursive panel factorization), then
+// columns, in order on one stream: factor P_k (the recursive panel factorization, or
+// left-looking by column under GPMI_PANEL=col), then
 // one trailing SYRK over all columns right of it (kdim = 128 * outer). (Round 5
 // removed the look-ahead form, the panel chain of P_{k+1} on a second high-priority
 // stream beside the bulk update of P_k: at the batch-64 headline 1441.8 against
@@ -215,17 +231,15 @@ int factor_panel(gpmi_op* op, const BatchPtrs& P, int b0, int nb, hipStream_t st
 // SYRK keeps every CU busy, so the chain beside it gains nothing.)
 // P points at batch member b0 (a batch group); `main` replaces op->stream.
 int schedule(gpmi_op* op, const BatchPtrs& P, int b0, int nb, hipStream_t main = nullptr) {
-  const int nt = op->nt, O = op->outer;
   hipStream_t A = main ? main : op->stream;
-  for (int c0 = 0; c0 < nt; c0 += O) {
-    const int W = std::min(O, nt - c0);
-    int rc = factor_panel(op, P, b0, nb, A, c0, W);
-    if (rc) return rc;
-    const int c1 = c0 + W;
-    if (c1 >= nt) break;
-    // the first trailing update reads its C tiles from K (run_factor copies only
-    // the first outer panel's tile columns into the members)
-    rc = launch_syrk(op, A, b0, nb, c1, nt - c1, nt - c1, c0 * TS, W * TS, c0 == 0);
+  for (const DenseLaunch& L : dense_plan(op->nt, op->outer, op->panel_mode)) {
+    // SYRK: a band update of the recursive schedule, or the bulk trailing update; the
+    // first bulk update reads its C tiles from K (run_factor copies only the first
+    // outer panel's tile columns into the members)
+    const int rc = L.kind == DENSE_SYRK
+                       ? launch_syrk(op, A, b0, nb, L.col, L.w, L.r1 - L.r0, L.p0, L.kdim,
+                                     L.from_k)
+                       : factor_panel(op, P, nb, A, L);
     if (rc) return rc;
   }
   return 0;
@@ -289,6 +303,7 @@ int run_factor(gpmi_op* op, const double* etas_host, int nb, const double* rhs_d
   }
   op->syrk_log.clear();
   op->syrk_shape.clear();
+  op->colpanel_ev_used = 0;
   op->cache_valid = false;
   ++op->factor_gen;
   if (op->timing) {
@@ -355,8 +370,9 @@ int collect_timing(gpmi_op* op) {
     tot += ms;
     fl += pr.second;
   }
-  if (std::getenv("GPMI_SYRK_TRACE")) {
-    // dev aid: SYRK time by class (bulk trailing update w == t vs band w < t) and kdim
+  if (op->trace) {
+    // dev aid: SYRK time by class (bulk trailing update w == t vs band w < t) and kdim,
+    // then the colpanel_kernel launches' total
     std::map<std::pair<int, int>, std::array<double, 3>> cls;
     for (size_t i = 0; i < op->syrk_log.size(); ++i) {
       const auto& sh = op->syrk_shape[i];
@@ -372,6 +388,15 @@ int collect_timing(gpmi_op* op) {
       fprintf(stderr, "[gpmi syrk] %s kdim=%4d launches=%3.0f ms=%8.3f TF/s=%6.2f\n",
               kv.first.first ? "bulk" : "band", kv.first.second, kv.second[0], kv.second[1],
               kv.second[2] / (kv.second[1] * 1e-3) / 1e12);
+    double cp = 0.0;
+    for (size_t i = 0; i + 1 < op->colpanel_ev_used; i += 2) {
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, op->colpanel_ev[i], op->colpanel_ev[i + 1]));
+      cp += ms;
+    }
+    if (op->colpanel_ev_used)
+      fprintf(stderr, "[gpmi syrk] colpanel_kernel launches=%3zu ms=%8.3f\n",
+              op->colpanel_ev_used / 2, cp);
   }
   std::sort(iv.begin(), iv.end());
   double busy = 0.0, cs = -1.0, ce = -1.0;
@@ -562,6 +587,17 @@ int gpmi_op_create(int device, int64_t n, int max_batch, gpmi_op** out) {
   op->nt = (int)(op->n_pad / TS);
   op->max_batch = max_batch;
   if (const char* g = std::getenv("GPMI_GROUPS")) op->groups = std::atoi(g);
+  if (const char* m = std::getenv("GPMI_PANEL")) {
+    // rec (the default: it measures faster): the recursive panel
+    // factorization (band SYRKs + panel_kernel); col: left-looking, one colpanel_kernel
+    // launch per panel column
+    if (!std::strcmp(m, "col")) op->panel_mode = DENSE_COL;
+    else if (std::strcmp(m, "rec") && *m) {
+      delete op;
+      return set_err(-1011, "GPMI_PANEL must be rec or col (got %s)", m);
+    }
+  }
+  op->trace = std::getenv("GPMI_SYRK_TRACE") != nullptr;
   const int64_t np = op->n_pad;
   auto fail = [&](hipError_t e, const char* what) {
     gpmi_op_destroy(op);
@@ -617,6 +653,7 @@ int gpmi_op_destroy(gpmi_op* op) {
   if (op->info) (void)hipFree(op->info);
   if (op->order) (void)hipFree(op->order);
   for (auto e : op->ev) (void)hipEventDestroy(e);
+  for (auto e : op->colpanel_ev) (void)hipEventDestroy(e);
   if (op->ev_begin) (void)hipEventDestroy(op->ev_begin);
   if (op->ev_end) (void)hipEventDestroy(op->ev_end);
   if (op->ev_fork) (void)hipEventDestroy(op->ev_fork);

@@ -16,6 +16,9 @@
 //                       partial, y_k = Linv_kk r_k, u_k = Linv_kk^T y_k, Gram y_k^T y_k
 //   panel_kernel      : L_ik = A_ik Linv_kk^T  and  r_i -= A_ik u_k  (= L_ik y_k)
 //   syrk_kernel       : A_ij -= sum_p L_ip L_jp^T over the lower-triangular tiles
+//   colpanel_kernel   : (GPMI_PANEL=col, left-looking) column k brought up to date from
+//                       the outer panel's earlier columns, then panel_kernel's step, then
+//                       the next diagonal tile, in one launch per panel column
 // All three are batched over the eta values (blockIdx.y / blockIdx.x = member).
 
 #include <hip/hip_runtime.h>
@@ -56,33 +59,19 @@ __global__ __launch_bounds__(256) void shift_copy_kernel(
 }
 
 // ---------------------------------------------------------------------------
-// Panel: for row tile I = kb + 1 + blockIdx.x of member b = blockIdx.y:
-//   L_Ik = A_Ik Linv_kk^T (in place)  and  r_I -= A_Ik u_k.
+// Panel step on the tile at Aik (row tile I, column kb) of one member, shared by
+// panel_kernel and colpanel_kernel:
+//   L_Ik = A_Ik Linv_kk^T (in place)  and  r_I -= A_Ik u_k  (u_k staged in sU).
+// Linv_kk is lower triangular: tile_trsm leaves out the block steps on its zero part.
 // ---------------------------------------------------------------------------
 #ifndef GPMI_PROBE_PANEL_NO_RHS
 #define GPMI_PROBE_PANEL_NO_RHS 0
 #endif
-__global__ __launch_bounds__(256, 2) void panel_kernel(BatchPtrs P, int64_t lda, int kb) {
-  __shared__ double smem[4 * STAGE + TS * RLD];
-  double* sA = smem;
-  double* sB = smem + 2 * STAGE;
-  double* sU = smem + 4 * STAGE;
+__device__ __forceinline__ void panel_step(double* Aik, int64_t lda, const double* Li,
+                                           double* R, double* sA, double* sB,
+                                           const double* sU) {
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int wr = w >> 1, wc = w & 1, fr = lane & 15, fk = lane >> 4;
-  const int b = blockIdx.y;
-  const int I = kb + 1 + blockIdx.x;
-  double* A = P.A + b * P.sA;
-  const double* U = P.U + b * P.sU;
-  if (!GPMI_PROBE_PANEL_NO_RHS) {
-    d2 v[4];
-#pragma unroll
-    for (int it = 0; it < 4; ++it)
-      v[it] = *reinterpret_cast<const d2*>(U + 2 * (it * 256 + t));
-#pragma unroll
-    for (int it = 0; it < 4; ++it) *reinterpret_cast<d2*>(&sU[2 * (it * 256 + t)]) = v[it];
-  }
-  double* Aik = A + (int64_t)I * TS * lda + (int64_t)kb * TS;
-  const double* Li = P.Linv + b * P.sL + (int64_t)kb * TS * TS;
   d4 acc[4][4];
   d4 racc[2];
 #pragma unroll
@@ -93,9 +82,9 @@ __global__ __launch_bounds__(256, 2) void panel_kernel(BatchPtrs P, int64_t lda,
 #if GPMI_PROBE_PANEL_NO_RHS
   // timing probe only (wrong results): the panel without its RHS operand, the bound on
   // what folding r_I -= L_Ik y_k into the SYRK could save (round 6, verdict item 7)
-  tile_mma<false>(Aik, lda, Li, TS, TS, sA, sB, acc, sU, racc);
+  tile_trsm<false>(Aik, lda, Li, sA, sB, acc, sU, racc);
 #else
-  tile_mma<true>(Aik, lda, Li, TS, TS, sA, sB, acc, sU, racc);
+  tile_trsm<true>(Aik, lda, Li, sA, sB, acc, sU, racc);
 #endif
   // C/D map of v_mfma_f64_16x16x4f64: row = (lane>>4) + 4*r, col = lane&15.
 #pragma unroll
@@ -104,9 +93,8 @@ __global__ __launch_bounds__(256, 2) void panel_kernel(BatchPtrs P, int64_t lda,
     for (int j = 0; j < 4; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r)
-        Aik[(int64_t)(wr * 64 + i * 16 + fk + 4 * r) * lda + wc * 64 + j * 16 + fr] =
+        Aik[(int64_t)(wr * 64 + i * 16 + fk + 4 * r) * lda + trsm_cb(wc, j) * 16 + fr] =
             acc[i][j][r];
-  double* R = P.R + b * P.sR + (int64_t)I * TS * RLD;
 #if GPMI_PROBE_PANEL_NO_RHS
   return;
 #endif
@@ -115,6 +103,111 @@ __global__ __launch_bounds__(256, 2) void panel_kernel(BatchPtrs P, int64_t lda,
 #pragma unroll
     for (int r = 0; r < 4; ++r)
       R[(wr * 64 + wc * 32 + h * 16 + fk + 4 * r) * RLD + fr] -= racc[h][r];
+}
+
+// u_k of member b into LDS (read after the first barrier of the operand pipeline)
+__device__ __forceinline__ void stage_u(const double* U, double* sU) {
+  const int t = threadIdx.x;
+  d2 v[4];
+#pragma unroll
+  for (int it = 0; it < 4; ++it) v[it] = *reinterpret_cast<const d2*>(U + 2 * (it * 256 + t));
+#pragma unroll
+  for (int it = 0; it < 4; ++it) *reinterpret_cast<d2*>(&sU[2 * (it * 256 + t)]) = v[it];
+}
+
+// Workgroup barrier that orders this workgroup's global stores before its later global
+// loads (a tile stored by some threads is read back by others).
+__device__ __forceinline__ void wg_global_barrier() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  __syncthreads();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// ---------------------------------------------------------------------------
+// Panel (the recursive schedule, the default): the panel step for row tile
+// I = kb + 1 + blockIdx.x of member b = blockIdx.y.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256, 2) void panel_kernel(BatchPtrs P, int64_t lda, int kb) {
+  __shared__ double smem[4 * STAGE + TS * RLD];
+  double* sU = smem + 4 * STAGE;
+  const int b = blockIdx.y;
+  const int I = kb + 1 + blockIdx.x;
+  double* A = P.A + b * P.sA;
+  if (!GPMI_PROBE_PANEL_NO_RHS) stage_u(P.U + b * P.sU, sU);
+  panel_step(A + (int64_t)I * TS * lda + (int64_t)kb * TS, lda,
+             P.Linv + b * P.sL + (int64_t)kb * TS * TS,
+             P.R + b * P.sR + (int64_t)I * TS * RLD, smem, smem + 2 * STAGE, sU);
+}
+
+// C tile <-> accumulators in the SYRK map (wave tile 64 x 64 at (wr, wc)).
+__device__ __forceinline__ void load_c(const double* C, int64_t lda, d4 (&acc)[4][4]) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int wr = wv >> 1, wc = wv & 1, fr = lane & 15, fk = lane >> 4;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        acc[a][c][r] = C[(int64_t)(wr * 64 + a * 16 + fk + 4 * r) * lda + wc * 64 + c * 16 + fr];
+}
+__device__ __forceinline__ void store_c(double* C, int64_t lda, const d4 (&acc)[4][4]) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int wr = wv >> 1, wc = wv & 1, fr = lane & 15, fk = lane >> 4;
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+#pragma unroll
+      for (int r = 0; r < 4; ++r)
+        C[(int64_t)(wr * 64 + a * 16 + fk + 4 * r) * lda + wc * 64 + c * 16 + fr] = acc[a][c][r];
+}
+
+// ---------------------------------------------------------------------------
+// Left-looking panel column kb of the outer panel that starts at tile column c0
+// (GPMI_PANEL=col), for row tile I = kb + 1 + blockIdx.x of member b = blockIdx.y:
+//   (a) A_Ik -= A_I,c0:k A_k,c0:k^T   (kdim = 128 (kb - c0); nothing at kb == c0)
+//   (b) the panel step on the tile just stored (read back through the slab path)
+//   (c) blockIdx.x == 0 (I = kb + 1) with next_diag set: the next diagonal tile,
+//       A_II -= A_I,c0:I A_I,c0:I^T (kdim = 128 (kb + 1 - c0)), its last slab the
+//       L_Ik of (b).
+// Every tile a workgroup reads is final before the launch or written by the workgroup
+// itself; every tile it writes is read by no other workgroup of the launch.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256, 2) void colpanel_kernel(BatchPtrs P, int64_t lda, int kb,
+                                                          int c0, int next_diag) {
+  __shared__ double smem[4 * STAGE + TS * RLD];
+  double* sA = smem;
+  double* sB = smem + 2 * STAGE;
+  double* sU = smem + 4 * STAGE;
+  const int b = blockIdx.y;
+  const int I = kb + 1 + blockIdx.x;
+  const int kdim = (kb - c0) * TS;
+  double* A = P.A + b * P.sA;
+  stage_u(P.U + b * P.sU, sU);
+  double* rowI = A + (int64_t)I * TS * lda;
+  double* Aik = rowI + (int64_t)kb * TS;
+  d4 dummy[2];
+  if (kdim > 0) {
+    d4 acc[4][4];
+    load_c(Aik, lda, acc);
+    tile_mma<false, true>(rowI + (int64_t)c0 * TS, lda,
+                          A + (int64_t)kb * TS * lda + (int64_t)c0 * TS, lda, kdim, sA, sB, acc,
+                          nullptr, dummy);
+    store_c(Aik, lda, acc);
+    wg_global_barrier();
+  }
+  panel_step(Aik, lda, P.Linv + b * P.sL + (int64_t)kb * TS * TS,
+             P.R + b * P.sR + (int64_t)I * TS * RLD, sA, sB, sU);
+  if (next_diag && blockIdx.x == 0) {
+    wg_global_barrier();
+    double* D = rowI + (int64_t)I * TS;
+    d4 acc[4][4];
+    load_c(D, lda, acc);
+    tile_mma<false, true>(rowI + (int64_t)c0 * TS, lda, rowI + (int64_t)c0 * TS, lda,
+                          kdim + TS, sA, sB, acc, nullptr, dummy);
+    store_c(D, lda, acc);
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -156,13 +249,7 @@ __global__ __launch_bounds__(256, 2) void syrk_kernel(double* A, int64_t lda, in
   double* C = Ab + (int64_t)I * TS * lda + (int64_t)J * TS;
   const double* Cin = Ksrc ? Ksrc + (int64_t)I * TS * lda + (int64_t)J * TS : C;
   d4 acc[4][4];
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        acc[a][c][r] = Cin[(int64_t)(wr * 64 + a * 16 + fk + 4 * r) * lda + wc * 64 + c * 16 + fr];
+  load_c(Cin, lda, acc);
   if (Ksrc && I == J && wr == wc) {
     // diagonal entries: a == c, row fk + 4 r == column fr
     const double eta = etas[blockIdx.y];
@@ -174,13 +261,7 @@ __global__ __launch_bounds__(256, 2) void syrk_kernel(double* A, int64_t lda, in
   }
   d4 dummy[2];
   tile_mma<false, true>(P1, lda, P2, lda, kdim, smem, smem + 2 * STAGE, acc, nullptr, dummy);
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int c = 0; c < 4; ++c)
-#pragma unroll
-      for (int r = 0; r < 4; ++r)
-        C[(int64_t)(wr * 64 + a * 16 + fk + 4 * r) * lda + wc * 64 + c * 16 + fr] = acc[a][c][r];
+  store_c(C, lda, acc);
 }
 
 // out[b][0] = logdet = sum of block partials; out[b][1 + e] = Gram entry e (16x16).

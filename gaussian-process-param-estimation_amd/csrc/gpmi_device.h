@@ -135,6 +135,72 @@ __device__ __forceinline__ void tile_mma(const double* __restrict__ P1, int64_t 
   }
 }
 
+// Output column block (16 wide, 0..7) that wave column wc computes as its j-th in
+// tile_trsm: {0, 3, 4, 7} and {1, 2, 5, 6}. Column block cb needs the k-slabs s <= cb,
+// so both wave columns run 18 of the 32 (slab, column block) steps.
+__device__ __forceinline__ int trsm_cb(int wc, int j) { return 2 * j + ((j ^ wc) & 1); }
+
+// acc += P1[0:128, 0:128] * Linv[0:128, 0:128]^T for a lower-triangular Linv (row-major,
+// ld 128), the wave's 64 rows (wr) x column blocks trsm_cb(wc, 0..3). Same slab pipeline
+// and, per accumulator, the same MFMA sequence as tile_mma over kdim = 128, except that
+// the steps whose Linv operand is identically zero (k-slab s > column block) are left
+// out: they add a * (+0) to a finite accumulator that started at +0. The racc update
+// (WITH_RHS, as in tile_mma) runs over every k.
+template <bool WITH_RHS>
+__device__ __forceinline__ void tile_trsm(const double* P1, int64_t ld1, const double* Linv,
+                                          double* sA, double* sB, d4 (&acc)[4][4],
+                                          const double* sU, d4 (&racc)[2]) {
+  const int t = threadIdx.x, lane = t & 63;
+  // the wave index as a scalar: the skips below are scalar branches
+  const int w = __builtin_amdgcn_readfirstlane(t >> 6);
+  const int wr = w >> 1, wc = w & 1;
+  const int fr = lane & 15, fk = lane >> 4;
+  d2 ra[4], rb[4];
+  gload_slab(P1, ld1, 0, ra);
+  gload_slab(Linv, TS, 0, rb);
+  sstore_slab(sA, ra);
+  sstore_slab(sB, rb);
+  __syncthreads();
+  constexpr int nsteps = TS / BK;
+#pragma unroll
+  for (int s = 0; s < nsteps; ++s) {
+    const int cur = s & 1;
+    const double* cA = sA + cur * STAGE;
+    const double* cB = sB + cur * STAGE;
+    if (s + 1 < nsteps) {
+      gload_slab(P1, ld1, (s + 1) * BK, ra);
+      gload_slab(Linv, TS, (s + 1) * BK, rb);
+    }
+#pragma unroll
+    for (int kk = 0; kk < BK / 4; ++kk) {
+      double a[4];
+#pragma unroll
+      for (int i = 0; i < 4; ++i) a[i] = cA[slab_off(wr * 64 + i * 16 + fr, kk * 4 + fk)];
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        // s <= 2 j: both wave columns; s == 2 j + 1: the one whose block is 2 j + 1
+        if (s <= 2 * j || (s == 2 * j + 1 && ((j ^ wc) & 1))) {
+          const double bj = cB[slab_off(trsm_cb(wc, j) * 16 + fr, kk * 4 + fk)];
+#pragma unroll
+          for (int i = 0; i < 4; ++i) acc[i][j] = mfma64(a[i], bj, acc[i][j]);
+        }
+      }
+      if (WITH_RHS) {
+        const double u = sU[(s * BK + kk * 4 + fk) * RLD + fr];
+        const double a0 = wc ? a[2] : a[0];
+        const double a1 = wc ? a[3] : a[1];
+        racc[0] = mfma64(a0, u, racc[0]);
+        racc[1] = mfma64(a1, u, racc[1]);
+      }
+    }
+    if (s + 1 < nsteps) {
+      sstore_slab(sA + (cur ^ 1) * STAGE, ra);
+      sstore_slab(sB + (cur ^ 1) * STAGE, rb);
+    }
+    __syncthreads();
+  }
+}
+
 // Bijective XCD-aware remap (consecutive logical tiles -> one XCD's L2).
 __device__ __forceinline__ int xcd_remap(int bid, int nwg) {
   const int xcd = bid & 7, q = nwg >> 3, r = nwg & 7;

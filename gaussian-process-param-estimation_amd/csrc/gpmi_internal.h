@@ -67,6 +67,7 @@ __global__ void shift_copy_kernel(const double* K, int64_t ldk, double* A, int64
                                   int wc);
 __global__ void diag_block_kernel(BatchPtrs P, int64_t lda, int kb, int nt);
 __global__ void panel_kernel(BatchPtrs P, int64_t lda, int kb);
+__global__ void colpanel_kernel(BatchPtrs P, int64_t lda, int kb, int c0, int next_diag);
 __global__ void syrk_kernel(double* A, int64_t lda, int64_t sA, int tc0, int w, int t,
                             int p0, int kdim, const uint32_t* order, const double* Ksrc,
                             const double* etas, int64_t n);
