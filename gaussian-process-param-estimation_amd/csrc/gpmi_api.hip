@@ -21,6 +21,7 @@
 #include "gpmi_host.h"
 #include "gpmi_band.h"
 #include "gpmi_dense_plan.h"
+#include "gpmi_predict_plan.h"
 #include "../../include/gpmi.h"
 
 using namespace gpmi;
@@ -90,6 +91,19 @@ struct gpmi_op {
   uint64_t tinv_gen = ~0ull;
   int tinv_have = 0;                   // bit 0: tr(A^-1), bit 1: tr(A^-2)
   double tinv[2] = {0.0, 0.0};
+  // prediction terms (gpmi_op_predict_terms; workspace allocated on first use)
+  double* PY = nullptr;      // [n_pad][16] Y = L^-1 rhs_src, kept where solve does not write
+  double* PT = nullptr;      // [wide][n_pad] the chunk's working block, transposed
+  double* Ppart = nullptr;   // [nt][wide][17] per-tile-row partials
+  double* Pout = nullptr;    // [wide][17]
+  double* Pgram = nullptr;   // [nt][256] partials, then [256] G = Y^T Y
+  int pred_wide = 0;         // columns the workspace holds
+  uint64_t rhs_gen = 0;      // bumped by gpmi_op_set_rhs
+  uint64_t ry_gen = ~0ull;   // factor generation for which R slot 0 holds L^-1 rhs_src
+  uint64_t ry_rhs = ~0ull;   // ... and the rhs generation
+  uint64_t py_gen = ~0ull, py_rhs = ~0ull;   // the same for PY / Pgram
+  std::vector<hipEvent_t> pred_ev;
+  double last_pred_ms = 0.0, last_pred_trail_ms = 0.0, last_pred_trail_flops = 0.0;
   // timing
   bool timing = false;
   std::vector<hipEvent_t> ev;
@@ -306,6 +320,9 @@ int run_factor(gpmi_op* op, const double* etas_host, int nb, const double* rhs_d
   op->colpanel_ev_used = 0;
   op->cache_valid = false;
   ++op->factor_gen;
+  // slot 0 of R ends as L^-1 rhs_src only when that block is what is factored along
+  op->ry_gen = rhs_dev == op->rhs_src ? op->factor_gen : ~0ull;
+  op->ry_rhs = op->rhs_gen;
   if (op->timing) {
     if (!op->ev_begin) {
       HIP_TRY(hipEventCreateWithFlags(&op->ev_begin, timing_event_flags()));
@@ -647,13 +664,14 @@ int gpmi_op_destroy(gpmi_op* op) {
   if (op->stream3) (void)hipStreamSynchronize(op->stream3);
   double* bufs[] = {op->K, op->A, op->R, op->X, op->U, op->Linv, op->logdiag, op->gram,
                     op->out, op->etas, op->rhs_src, op->scratch, op->scratch2, op->tracebuf,
-                    op->W, op->tpart, op->Td};
+                    op->W, op->tpart, op->Td, op->PY, op->PT, op->Ppart, op->Pout, op->Pgram};
   for (double* p : bufs)
     if (p) (void)hipFree(p);
   if (op->info) (void)hipFree(op->info);
   if (op->order) (void)hipFree(op->order);
   for (auto e : op->ev) (void)hipEventDestroy(e);
   for (auto e : op->colpanel_ev) (void)hipEventDestroy(e);
+  for (auto e : op->pred_ev) (void)hipEventDestroy(e);
   if (op->ev_begin) (void)hipEventDestroy(op->ev_begin);
   if (op->ev_end) (void)hipEventDestroy(op->ev_end);
   if (op->ev_fork) (void)hipEventDestroy(op->ev_fork);
@@ -740,6 +758,7 @@ int gpmi_op_set_rhs(gpmi_op* op, const double* rhs, int64_t ld, int nrhs) {
   int rc = upload_rhs(op, op->rhs_src, rhs, ld, nrhs, 0);
   if (rc) return rc;
   op->nrhs = nrhs;
+  ++op->rhs_gen;
   return 0;
 }
 
@@ -816,6 +835,7 @@ int gpmi_op_solve(gpmi_op* op, double eta, const double* rhs, int64_t ld, int nr
     bool fresh;
     rc = ensure_factor(op, eta, op->scratch, &fresh);
     if (rc) return rc;
+    op->ry_gen = ~0ull;   // R is overwritten below (gpmi_op_predict_terms keeps its own Y)
     int inf = 0;
     HIP_TRY(hipMemcpyAsync(&inf, op->info, sizeof(int), hipMemcpyDeviceToHost, op->stream));
     HIP_TRY(hipStreamSynchronize(op->stream));
@@ -979,6 +999,220 @@ int gpmi_op_traceinv(gpmi_op* op, double eta, int exponent, double* value) {
     }
   }
   *value = op->tinv[exponent - 1];
+  return 0;
+}
+
+int gpmi_matern_cross(int device, const double* points, int64_t n, const double* test_points,
+                      int64_t nstar, int d, const double* scale, double nu, double* C_out,
+                      int64_t ldc) {
+  if (!points || !test_points || !scale || !C_out) return set_err(-1004, "null argument");
+  if (n < 1 || nstar < 1) return set_err(-1005, "point counts must be positive");
+  if (d < 1 || d > GPMI_MAX_DIM)
+    return set_err(-1003, "dimension %d outside [1, %d]", d, GPMI_MAX_DIM);
+  MaternParams P;
+  int rc = matern_params(nu, &P);
+  if (rc) return rc;
+  DeviceGuard g(device);
+  DevBuf<double> dp, dt, ds, dC;
+  HIP_TRY(dp.reserve((size_t)n * d));
+  HIP_TRY(dt.reserve((size_t)nstar * d));
+  HIP_TRY(ds.reserve(d));
+  HIP_TRY(dC.reserve((size_t)nstar * n));
+  HIP_TRY(hipMemcpy(dp, points, sizeof(double) * n * d, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(dt, test_points, sizeof(double) * nstar * d, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(ds, scale, sizeof(double) * d, hipMemcpyHostToDevice));
+  launch_matern_cross(nullptr, dp, n, dt, nstar, d, ds, P, dC, n, nstar, n);
+  LAUNCH_CHECK("matern_cross_kernel");
+  HIP_TRY(hipMemcpy2D(C_out, sizeof(double) * ldc, dC, sizeof(double) * n, sizeof(double) * n,
+                      nstar, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// Y = L^-1 rhs_src for the cached factor into PY, and G = Y^T Y into Pgram[0..256):
+// from slot 0 of R when it still holds Y, else by forward substitution of rhs_src
+// again (a solve since the factorization has overwritten R).
+static int predict_refresh_y(gpmi_op* op) {
+  if (op->py_gen == op->factor_gen && op->py_rhs == op->rhs_gen) return 0;
+  hipStream_t s = op->stream;
+  BatchPtrs P = op->ptrs();
+  if (op->ry_gen != op->factor_gen || op->ry_rhs != op->rhs_gen) {
+    HIP_TRY(hipMemcpyAsync(op->R, op->rhs_src, sizeof(double) * P.sR, hipMemcpyDeviceToDevice,
+                           s));
+    for (int kb = 0; kb < op->nt; ++kb) {
+      hipLaunchKernelGGL(fwd_step_kernel, dim3(op->nt - kb, 1), dim3(256), 0, s, P, op->n_pad,
+                         kb);
+      LAUNCH_CHECK("fwd_step_kernel");
+    }
+    op->ry_gen = op->factor_gen;
+    op->ry_rhs = op->rhs_gen;
+  }
+  HIP_TRY(hipMemcpyAsync(op->PY, op->R, sizeof(double) * P.sR, hipMemcpyDeviceToDevice, s));
+  hipLaunchKernelGGL(pred_gram_kernel, dim3(op->nt), dim3(256), 0, s, op->PY,
+                     op->Pgram + 256);
+  LAUNCH_CHECK("pred_gram_kernel");
+  hipLaunchKernelGGL(pred_reduce_kernel, dim3(1), dim3(256), 0, s, op->Pgram + 256, op->nt,
+                     (int64_t)256, op->Pgram);
+  LAUNCH_CHECK("pred_reduce_kernel");
+  op->py_gen = op->factor_gen;
+  op->py_rhs = op->rhs_gen;
+  return 0;
+}
+
+int gpmi_op_predict_terms(gpmi_op* op, double eta, const double* points, int d,
+                          const double* scale, double nu, const double* test_points,
+                          int64_t nstar, const double* kstar, int64_t ldks, double* c_out,
+                          double* q_out, double* gram_out) {
+  if (!op) return set_err(-1006, "null handle");
+  if (!op->has_K) return set_err(-1000, "operator has no matrix (load or assemble first)");
+  if (op->nrhs < 1) return set_err(-1012, "no resident right-hand sides (gpmi_op_set_rhs)");
+  if (nstar < 1) return set_err(-1013, "nstar must be positive (got %lld)", (long long)nstar);
+  MaternParams MP;
+  if (!kstar) {
+    if (d < 1 || d > GPMI_MAX_DIM)
+      return set_err(-1003, "dimension %d outside [1, %d]", d, GPMI_MAX_DIM);
+    if (!points || !scale || !test_points) return set_err(-1004, "null argument");
+    int rc = matern_params(nu, &MP);
+    if (rc) return rc;
+  } else if (ldks < op->n) {
+    return set_err(-1014, "ldks %lld below n = %lld", (long long)ldks, (long long)op->n);
+  }
+  int64_t knob = 0;   // GPMI_PREDICT_CHUNK: the chunk width in columns (read per call)
+  if (const char* e = std::getenv("GPMI_PREDICT_CHUNK"))
+    if (*e) knob = std::atoll(e) > 0 ? std::atoll(e) : -1;
+  const int64_t np = op->n_pad, n = op->n;
+  const int nt = op->nt;
+  const int NS = predict_chunk_cols(np, knob);
+  if (NS < 0) return set_err(-1015, "GPMI_PREDICT_CHUNK must be a positive multiple of 128");
+  DeviceGuard g(op->device);
+  hipStream_t s = op->stream;
+  bool fresh;
+  int rc = ensure_factor(op, eta, op->rhs_src, &fresh);
+  if (rc) return rc;
+  int inf = 0;
+  HIP_TRY(hipMemcpyAsync(&inf, op->info, sizeof(int), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (inf) {
+    op->cache_valid = false;
+    return set_err(inf, "matrix K + eta I is not positive definite (pivot %d)", inf);
+  }
+  // workspace: grown to the widest chunk a call has needed, at most NS columns
+  const int wide = (int)std::min<int64_t>(NS, (nstar + TS - 1) / TS * TS);
+  if (!op->PY) {
+    HIP_TRY(hipMalloc(&op->PY, sizeof(double) * (size_t)np * RLD));
+    HIP_TRY(hipMalloc(&op->Pgram, sizeof(double) * (size_t)(nt + 1) * 256));
+  }
+  if (op->pred_wide < wide) {
+    const PredictSizes sz = predict_sizes(np, nt, wide);
+    for (double** p : {&op->PT, &op->Ppart, &op->Pout}) {
+      if (*p) HIP_TRY(hipFree(*p));
+      *p = nullptr;
+    }
+    op->pred_wide = 0;
+    HIP_TRY(hipMalloc(&op->PT, sizeof(double) * sz.T));
+    HIP_TRY(hipMalloc(&op->Ppart, sizeof(double) * sz.part));
+    HIP_TRY(hipMalloc(&op->Pout, sizeof(double) * sz.out));
+    op->pred_wide = wide;
+  }
+  const std::vector<PredictLaunch> plan = predict_plan(nt, predict_outer(op->outer));
+  size_t nev = 2;
+  for (const PredictLaunch& L : plan) nev += L.kind == PRED_TRAIL ? 2 : 0;
+  const std::vector<PredictChunk> chunks = predict_chunks(nstar, NS);
+  if (op->timing) {
+    nev = 2 + (nev - 2) * chunks.size();
+    while (op->pred_ev.size() < nev) {
+      hipEvent_t e;
+      HIP_TRY(hipEventCreateWithFlags(&e, timing_event_flags()));
+      op->pred_ev.push_back(e);
+    }
+    HIP_TRY(hipEventRecord(op->pred_ev[0], s));
+  }
+  if ((rc = predict_refresh_y(op))) return rc;
+  DevBuf<double> dp, dt, ds;
+  if (!kstar) {
+    HIP_TRY(dp.reserve((size_t)n * d));
+    HIP_TRY(dt.reserve((size_t)nstar * d));
+    HIP_TRY(ds.reserve(d));
+    HIP_TRY(hipMemcpyAsync(dp, points, sizeof(double) * n * d, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipMemcpyAsync(dt, test_points, sizeof(double) * nstar * d, hipMemcpyHostToDevice,
+                           s));
+    HIP_TRY(hipMemcpyAsync(ds, scale, sizeof(double) * d, hipMemcpyHostToDevice, s));
+  }
+  std::vector<double> h((size_t)wide * PRED_LD);
+  const int m = op->nrhs;
+  size_t evi = 2;
+  double trail_flops = 0.0;
+  for (const PredictChunk& ch : chunks) {
+    const int nct = ch.nct;
+    const int64_t rows = (int64_t)nct * TS;   // rows of T this chunk runs (<= wide)
+    if (kstar) {
+      HIP_TRY(hipMemsetAsync(op->PT, 0, sizeof(double) * rows * np, s));
+      HIP_TRY(hipMemcpy2DAsync(op->PT, sizeof(double) * np, kstar + ch.j0 * ldks,
+                               sizeof(double) * ldks, sizeof(double) * n, ch.cols,
+                               hipMemcpyHostToDevice, s));
+    } else {
+      launch_matern_cross(s, dp, n, static_cast<double*>(dt) + ch.j0 * d, ch.cols, d, ds, MP,
+                          op->PT, np, rows, np);
+      LAUNCH_CHECK("matern_cross_kernel");
+    }
+    for (const PredictLaunch& L : plan) {
+      if (L.kind == PRED_DIAG) {
+        hipLaunchKernelGGL(pred_diag_kernel, dim3(nct), dim3(256), 0, s, op->A, np, op->Linv,
+                           op->PY, op->PT, np, L.r0, L.kb, op->Ppart, rows);
+        LAUNCH_CHECK("pred_diag_kernel");
+      } else {
+        const int ni = L.r1 - L.r0;
+        if (op->timing) HIP_TRY(hipEventRecord(op->pred_ev[evi++], s));
+        hipLaunchKernelGGL(pred_update_kernel, dim3(ni * nct), dim3(256), 0, s, op->A, np,
+                           op->PT, np, L.r0, ni, nct, L.kb, L.ke);
+        LAUNCH_CHECK("pred_update_kernel");
+        if (op->timing) HIP_TRY(hipEventRecord(op->pred_ev[evi++], s));
+        trail_flops += 2.0 * TS * TS * (double)(L.ke - L.kb) * TS * ni * nct;
+      }
+    }
+    const int64_t cnt = rows * PRED_LD;
+    hipLaunchKernelGGL(pred_reduce_kernel, dim3((unsigned)((cnt + 255) / 256)), dim3(256), 0, s,
+                       op->Ppart, nt, cnt, op->Pout);
+    LAUNCH_CHECK("pred_reduce_kernel");
+    HIP_TRY(hipMemcpyAsync(h.data(), op->Pout, sizeof(double) * ch.cols * PRED_LD,
+                           hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int j = 0; j < ch.cols; ++j) {
+      if (c_out)
+        for (int a = 0; a < m; ++a) c_out[(ch.j0 + j) * m + a] = h[(size_t)j * PRED_LD + a];
+      if (q_out) q_out[ch.j0 + j] = h[(size_t)j * PRED_LD + 16];
+    }
+  }
+  if (gram_out) {
+    double hg[256];
+    HIP_TRY(hipMemcpyAsync(hg, op->Pgram, sizeof(hg), hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    for (int a = 0; a < m; ++a)
+      for (int c = 0; c < m; ++c) gram_out[a * m + c] = hg[a * RLD + c];
+  }
+  op->last_pred_ms = op->last_pred_trail_ms = op->last_pred_trail_flops = 0.0;
+  if (op->timing) {
+    HIP_TRY(hipEventRecord(op->pred_ev[1], s));
+    HIP_TRY(hipEventSynchronize(op->pred_ev[1]));
+    float ms = 0.f;
+    HIP_TRY(hipEventElapsedTime(&ms, op->pred_ev[0], op->pred_ev[1]));
+    op->last_pred_ms = ms;
+    double tr = 0.0;
+    for (size_t e = 2; e + 1 < evi; e += 2) {
+      HIP_TRY(hipEventElapsedTime(&ms, op->pred_ev[e], op->pred_ev[e + 1]));
+      tr += ms;
+    }
+    op->last_pred_trail_ms = tr;
+    op->last_pred_trail_flops = trail_flops;
+  }
+  return 0;
+}
+
+int gpmi_op_predict_ms(gpmi_op* op, double* total_ms, double* trailing_ms,
+                       double* trailing_flops) {
+  if (!op) return set_err(-1006, "null handle");
+  if (total_ms) *total_ms = op->last_pred_ms;
+  if (trailing_ms) *trailing_ms = op->last_pred_trail_ms;
+  if (trailing_flops) *trailing_flops = op->last_pred_trail_flops;
   return 0;
 }
 

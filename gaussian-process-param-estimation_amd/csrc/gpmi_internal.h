@@ -88,6 +88,21 @@ __global__ void gram_sumsq_kernel(const double* W, int64_t ldw, const double* Td
                                   double* partial);
 __global__ void matern_eval_kernel(const double* x, int64_t m, MaternParams P, double* out);
 
+// Cross Matérn assembly C[j][i] = matern(test_j, points_i), zero for j >= ns or i >= n;
+// rows x cols entries are written (gpmi_matern.hip).
+void launch_matern_cross(hipStream_t s, const double* points, int64_t n, const double* test,
+                         int64_t ns, int d, const double* scale, const MaternParams& P,
+                         double* C, int64_t ldc, int64_t rows, int64_t cols);
+
+// Prediction terms (gpmi_predict.hip; launch list in gpmi_predict_plan.h).
+__global__ void pred_update_kernel(const double* L, int64_t lda, double* T, int64_t ldt, int i0,
+                                   int ni, int nct, int kb, int ke);
+__global__ void pred_diag_kernel(const double* L, int64_t lda, const double* Linv,
+                                 const double* Y, double* T, int64_t ldt, int k, int kb,
+                                 double* part, int64_t ns_ld);
+__global__ void pred_reduce_kernel(const double* part, int nt, int64_t cnt, double* out);
+__global__ void pred_gram_kernel(const double* Y, double* gpart);
+
 // Multi-shift CG Gram state (gpmi_sparse.hip, gpmi_sparse_api.hip); device pointers.
 #ifndef GPMI_LZ_JC
 #define GPMI_LZ_JC 16

@@ -247,6 +247,72 @@ void launch_matern_dense(dim3 grid, hipStream_t s, const double* points, int64_t
   }
 }
 
+// Cross-correlation of two point sets, for prediction: one workgroup = one 64 x 64 tile
+// of C[j][i] = matern(scaled distance(test_j, points_i)), row j a test point, column i a
+// training point (the row-major [n*][n] block whose transpose the wide forward
+// substitution of gpmi_predict.hip solves in place). Same scaled_distance / matern_value
+// as the dense kernel above, the test point in the row role: (a - b)^2 == (b - a)^2 bit
+// for bit, so a test point equal to a training point reproduces K's entry exactly. No
+// symmetry, so no mirrored store. Entries with j >= ns or i >= n are ZERO (right-hand
+// sides, not the identity pad); only j < rows, i < cols is written.
+template <int MODE>
+__global__ __launch_bounds__(256, GPMI_MATERN_MINB) void matern_cross_kernel_t(
+    const double* __restrict__ points, int64_t n, const double* __restrict__ test, int64_t ns,
+    int d, const double* __restrict__ scale_dev, MaternParams P, double* __restrict__ C,
+    int64_t ldc, int64_t rows, int64_t cols) {
+  __shared__ double srow[MT * GPMI_MAX_DIM];
+  __shared__ double sscale[GPMI_MAX_DIM], srs[GPMI_MAX_DIM];
+  const int t = threadIdx.x, c = t & (MT - 1), r0 = t >> 6;
+  const int64_t i0 = (int64_t)blockIdx.x * MT, j0 = (int64_t)blockIdx.y * MT;
+  if (t < d) {
+    sscale[t] = scale_dev[t];
+    srs[t] = 1.0 / scale_dev[t];
+  }
+  for (int e = t; e < MT * d; e += 256) {
+    const int64_t j = j0 + e / d;
+    srow[e] = (j < ns) ? test[j * d + (e % d)] : 0.0;
+  }
+  __syncthreads();
+  const int64_t i = i0 + c;
+  double pi[GPMI_MAX_DIM];
+#pragma unroll
+  for (int k = 0; k < GPMI_MAX_DIM; ++k) pi[k] = (k < d && i < n) ? points[i * d + k] : 0.0;
+#pragma unroll
+  for (int q = 0; q < MT / 4; ++q) {
+    const int r = r0 + 4 * q;
+    const int64_t j = j0 + r;
+    double v = 0.0;
+    if (i < n && j < ns)
+      v = matern_value<MODE>(scaled_distance(&srow[r * d], pi, sscale, srs, d), P);
+    if (j < rows && i < cols) C[j * ldc + i] = v;
+  }
+}
+
+// Per-nu dispatch as launch_matern_dense. Grid: ceil(cols / 64) x ceil(rows / 64).
+void launch_matern_cross(hipStream_t s, const double* points, int64_t n, const double* test,
+                         int64_t ns, int d, const double* scale, const MaternParams& P,
+                         double* C, int64_t ldc, int64_t rows, int64_t cols) {
+  const dim3 grid((unsigned)((cols + MT - 1) / MT), (unsigned)((rows + MT - 1) / MT));
+  switch (P.mode) {
+    case MATERN_HALF:
+      hipLaunchKernelGGL(matern_cross_kernel_t<MATERN_HALF>, grid, dim3(256), 0, s, points, n,
+                         test, ns, d, scale, P, C, ldc, rows, cols);
+      break;
+    case MATERN_3HALF:
+      hipLaunchKernelGGL(matern_cross_kernel_t<MATERN_3HALF>, grid, dim3(256), 0, s, points, n,
+                         test, ns, d, scale, P, C, ldc, rows, cols);
+      break;
+    case MATERN_5HALF:
+      hipLaunchKernelGGL(matern_cross_kernel_t<MATERN_5HALF>, grid, dim3(256), 0, s, points, n,
+                         test, ns, d, scale, P, C, ldc, rows, cols);
+      break;
+    default:
+      hipLaunchKernelGGL(matern_cross_kernel_t<-1>, grid, dim3(256), 0, s, points, n, test, ns,
+                         d, scale, P, C, ldc, rows, cols);
+      break;
+  }
+}
+
 }  // namespace gpmi
 
 // ---------------------------------------------------------------------------

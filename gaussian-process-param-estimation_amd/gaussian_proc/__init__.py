@@ -10,7 +10,8 @@ CPU fallback.
 """
 
 from .generate_correlation import generate_correlation, DeviceCorrelation   # noqa: F401
+from .generate_correlation import generate_cross_correlation               # noqa: F401
 from .gaussian_process import GaussianProcess                              # noqa: F401
 from .__version__ import __version__                                       # noqa: F401
 
-__all__ = ['GaussianProcess', 'generate_correlation']
+__all__ = ['GaussianProcess', 'generate_correlation', 'generate_cross_correlation']

@@ -54,6 +54,14 @@ SIGNATURES = {
     'gpmi_op_last_timing': (ctypes.c_int, [c_op_p, c_double_p, c_int_p, c_double_p,
                                            c_double_p, c_double_p]),
     'gpmi_op_set_outer': (ctypes.c_int, [c_op_p, ctypes.c_int]),
+    'gpmi_matern_cross': (ctypes.c_int, [ctypes.c_int, c_double_p, c_i64, c_double_p, c_i64,
+                                         ctypes.c_int, c_double_p, ctypes.c_double, c_double_p,
+                                         c_i64]),
+    'gpmi_op_predict_terms': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p, ctypes.c_int,
+                                             c_double_p, ctypes.c_double, c_double_p, c_i64,
+                                             c_double_p, c_i64, c_double_p, c_double_p,
+                                             c_double_p]),
+    'gpmi_op_predict_ms': (ctypes.c_int, [c_op_p, c_double_p, c_double_p, c_double_p]),
     'gpmi_last_assembly_ms': (ctypes.c_int, [c_double_p]),
     'gpmi_matern_values': (ctypes.c_int, [ctypes.c_int, c_double_p, c_i64, ctypes.c_double,
                                           c_double_p]),
@@ -327,6 +335,53 @@ class Operator(object):
     def set_outer(self, s):
         check(self.lib.gpmi_op_set_outer(self.h, int(s)), 'gpmi_op_set_outer')
 
+    def predict_terms(self, eta, test_points=None, points=None, scale=None, nu=None,
+                      cross=None):
+        """-> (c[nstar, nrhs], q[nstar], gram[nrhs, nrhs]) for the resident RHS R
+        and the factor K + eta I = L L^T: c_j = R^T (K + eta I)^-1 k*_j,
+        q_j = k*_j^T (K + eta I)^-1 k*_j, gram = R^T (K + eta I)^-1 R
+        (gpmi_op_predict_terms). k*_j, the correlations of test point j with the
+        training points, is assembled on the device from ``points`` (n x d, the
+        training points), ``scale`` (d), ``nu`` and ``test_points`` (nstar x d), or
+        taken from the host matrix ``cross`` (nstar x n)."""
+        m = self.nrhs
+        if cross is not None:
+            cross = as_c(cross)
+            if cross.ndim != 2 or cross.shape[1] != self.n or cross.shape[0] < 1:
+                raise ValueError('cross must be nstar x %d with nstar >= 1' % self.n)
+            nstar = cross.shape[0]
+            args = (None, 0, None, 0.0, None, nstar, dptr(cross), self.n)
+        else:
+            if test_points is None or points is None or scale is None or nu is None:
+                raise ValueError('predict_terms needs test_points, points, scale and nu, '
+                                 'or cross')
+            points = as_c(points)
+            test_points = as_c(test_points)
+            scale = as_c(scale)
+            if points.ndim != 2 or points.shape[0] != self.n:
+                raise ValueError('points must be %d x d' % self.n)
+            d = points.shape[1]
+            if test_points.ndim != 2 or test_points.shape[1] != d or test_points.shape[0] < 1:
+                raise ValueError('test_points must be nstar x %d with nstar >= 1' % d)
+            if scale.shape != (d,):
+                raise ValueError('scale must have one entry per dimension (%d)' % d)
+            nstar = test_points.shape[0]
+            args = (dptr(points), d, dptr(scale), float(nu), dptr(test_points), nstar, None, 0)
+        c = numpy.empty((nstar, m))
+        q = numpy.empty(nstar)
+        g = numpy.empty((m, m))
+        check(self.lib.gpmi_op_predict_terms(self.h, float(eta), *args, dptr(c), dptr(q),
+                                             dptr(g)), 'gpmi_op_predict_terms')
+        return c, q, g
+
+    def predict_ms(self):
+        """-> dict(total_ms, trailing_ms, trailing_flops) of the last predict_terms
+        with set_timing(True) (HIP events)."""
+        a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        check(self.lib.gpmi_op_predict_ms(self.h, ctypes.byref(a), ctypes.byref(b),
+                                          ctypes.byref(c)), 'gpmi_op_predict_ms')
+        return dict(total_ms=a.value, trailing_ms=b.value, trailing_flops=c.value)
+
 
 class Band(object):
     """Owning wrapper of a ``gpmi_band`` handle: the operator's K reduced once on
@@ -541,6 +596,25 @@ def matern_dense(points, scale, nu, device=None):
     check(lib.gpmi_matern_dense(device, dptr(points), n, d, dptr(scale), float(nu), dptr(K),
                                 n), 'gpmi_matern_dense')
     return K
+
+
+def matern_cross(test_points, points, scale, nu, device=None):
+    """Matérn cross-correlation of test_points (nstar x d) with points (n x d) on
+    the device, returned as a host ndarray (nstar, n)."""
+    lib = load()
+    device = default_device() if device is None else int(device)
+    require_device(device)
+    points = as_c(points)
+    test_points = as_c(test_points)
+    scale = as_c(scale)
+    n, d = points.shape
+    nstar = test_points.shape[0]
+    C = numpy.empty((nstar, n))
+    if nstar == 0 or n == 0:
+        return C
+    check(lib.gpmi_matern_cross(device, dptr(points), n, dptr(test_points), nstar, d,
+                                dptr(scale), float(nu), dptr(C), n), 'gpmi_matern_cross')
+    return C
 
 
 def last_assembly_ms():

@@ -55,6 +55,47 @@ def _der_from_terms(n, m, G1, G2, G3, tr1, tr2=None):
     return der1, der2
 
 
+def _predict_from_terms(c, q, G, Phi_star, sigma, sigma0, noise=False):
+    """Posterior mean and variance at n* new points (universal kriging) from the
+    prediction terms of MixedCorrelation.predict_terms. With S = K + eta I,
+    eta = (sigma0 / sigma)^2, R = [X z] and k*_j the correlations of new point j
+    with the training points:
+      c[j]  = R^T S^-1 k*_j            (n* x (m + 1))
+      q[j]  = k*_j^T S^-1 k*_j         (n*)
+      G     = R^T S^-1 R               ((m + 1) x (m + 1))
+    and Phi_star (n* x m) the basis rows of the new points. Then, with B = G_XX,
+      beta  = B^-1 G_Xz
+      mean  = Phi_star beta + c_z - c_X beta        (= phi beta + k*^T S^-1 (z - X beta))
+      var   = sigma^2 (1 - q + r^T B^-1 r),  r = phi - c_X   (the latent function;
+              ``noise`` adds sigma0^2)
+    m = 0 (no basis) leaves mean = c_z and var = sigma^2 (1 - q). -> (mean, var)."""
+    c = numpy.asarray(c, dtype=float)
+    q = numpy.asarray(q, dtype=float)
+    G = numpy.asarray(G, dtype=float)
+    m = G.shape[0] - 1
+    if m < 0 or G.shape != (m + 1, m + 1) or c.ndim != 2 or c.shape[1] != m + 1 or \
+            q.shape != (c.shape[0],):
+        raise ValueError('c must be n* x (m + 1), q n* and G (m + 1) x (m + 1)')
+    Phi = numpy.asarray(Phi_star, dtype=float).reshape(c.shape[0], -1)
+    if Phi.shape[1] != m:
+        raise ValueError('Phi_star must be n* x %d' % m)
+    if not sigma > 0.0:
+        raise ValueError('sigma must be positive')
+    var = 1.0 - q
+    if m == 0:
+        mean = c[:, 0].copy()
+    else:
+        B = G[:m, :m]
+        beta = numpy.linalg.solve(B, G[:m, m])
+        mean = Phi @ beta + (c[:, m] - c[:, :m] @ beta)
+        r = Phi - c[:, :m]
+        var = var + numpy.sum(r * numpy.linalg.solve(B, r.T).T, axis=1)
+    var = sigma ** 2 * var
+    if noise:
+        var = var + sigma0 ** 2
+    return mean, var
+
+
 class ProfileLikelihood(object):
 
     @staticmethod

@@ -1,7 +1,11 @@
 """Gaussian process user class (drop-in for
-gaussian_proc/gaussian_process/gaussian_process.py:21-71)."""
+gaussian_proc/gaussian_process/gaussian_process.py:21-71), with the prediction
+the reference leaves as a commented-out stub."""
+
+import numpy
 
 from .._likelihood import Likelihood
+from .._likelihood._profile_likelihood import _predict_from_terms
 
 __all__ = ['GaussianProcess']
 
@@ -16,8 +20,56 @@ class GaussianProcess(object):
         self.K = K
         self.likelihood = Likelihood(X, K, likelihood_method=likelihood_method,
                                      device=device)
+        self.z = None
+        self.results = None
 
     def train(self, z, plot=False):
-        """Find the hyperparameters; prints the results dict (reference :154-162)."""
+        """Find the hyperparameters; prints the results dict (reference :154-162)
+        and keeps it, with z, for ``predict``."""
         results = self.likelihood.maximize_log_likelihood(z, plot=plot)
         print(results)
+        self.z = numpy.asarray(z, dtype=float).copy()
+        self.results = results
+
+    def predict(self, test_points, X_star, z=None, hyperparam=None, noise=False,
+                return_var=True, **kernel_params):
+        """Posterior mean (and variance) at ``test_points`` (n* x d) with basis rows
+        ``X_star`` (n* x m): universal kriging with the fitted or given
+        ``hyperparam = (sigma, sigma0)``,
+          mean = phi* beta + k*^T S^-1 (z - X beta),
+          var  = sigma^2 (1 - k*^T S^-1 k* + r^T (X^T S^-1 X)^-1 r),
+                 r = phi* - X^T S^-1 k*,  S = K + (sigma0 / sigma)^2 I,
+        the variance of the latent function (``noise=True`` adds sigma0^2). ``z`` and
+        ``hyperparam`` default to those of the last ``train``. The cross-correlation
+        k* is assembled on the device from the kernel parameters of a
+        DeviceCorrelation K; an ndarray K needs ``points``, ``correlation_scale``
+        and ``nu`` (or ``cross``, the n* x n matrix itself) as keywords.
+        -> mean, or (mean, var) with ``return_var``."""
+        if z is None:
+            z = self.z
+        if hyperparam is None and self.results is not None:
+            hyperparam = (self.results['sigma'], self.results['sigma0'])
+        if z is None or hyperparam is None:
+            raise ValueError('predict needs z and hyperparam=(sigma, sigma0), or an earlier '
+                             'train(z)')
+        bad = sorted(set(kernel_params) - {'points', 'correlation_scale', 'nu', 'cross'})
+        if bad:
+            raise TypeError('predict: unexpected keyword argument %s' % ', '.join(map(repr, bad)))
+        sigma, sigma0 = float(hyperparam[0]), float(hyperparam[1])
+        if not sigma > 0.0:
+            raise ValueError('sigma must be positive')
+        X = numpy.asarray(self.X, dtype=float)
+        n, m = X.shape
+        z = numpy.asarray(z, dtype=float)
+        if z.shape != (n,):
+            raise ValueError('z must have %d entries' % n)
+        test_points = numpy.asarray(test_points, dtype=float)
+        if test_points.ndim != 2 or test_points.shape[0] < 1:
+            raise ValueError('test_points must be a 2D array (n*, dimension) with n* >= 1')
+        X_star = numpy.asarray(X_star, dtype=float)
+        if X_star.shape != (test_points.shape[0], m):
+            raise ValueError('X_star must be %d x %d' % (test_points.shape[0], m))
+        c, q, G = self.likelihood.K_mixed.predict_terms((sigma0 / sigma) ** 2, X, z,
+                                                        test_points=test_points, **kernel_params)
+        mean, var = _predict_from_terms(c, q, G, X_star, sigma, sigma0, noise=noise)
+        return (mean, var) if return_var else mean

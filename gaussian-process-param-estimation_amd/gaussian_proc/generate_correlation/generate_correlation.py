@@ -16,7 +16,8 @@ import numpy
 
 from .. import _hip
 
-__all__ = ['generate_correlation', 'DeviceCorrelation', 'DeviceSparseCorrelation']
+__all__ = ['generate_correlation', 'generate_cross_correlation', 'DeviceCorrelation',
+           'DeviceSparseCorrelation']
 
 
 class DeviceCorrelation(object):
@@ -106,3 +107,20 @@ def generate_correlation(points, correlation_scale=0.1, nu=0.5, grid=True, spars
     if verbose:
         print('Generated dense correlation matirx of size: %d.' % points.shape[0])
     return K
+
+
+def generate_cross_correlation(test_points, points, correlation_scale=0.1, nu=0.5, device=None):
+    """Matérn correlation of ``test_points`` (n* x d) with ``points`` (n x d):
+    ``numpy.ndarray`` (n*, n), entry [j, i] the correlation of test point j with
+    point i, from the same device arithmetic as ``generate_correlation`` (a test
+    point equal to a training point reproduces that matrix's entry bit for bit).
+    The reference has no counterpart (it does not predict)."""
+    points = numpy.ascontiguousarray(points, dtype=float)
+    test_points = numpy.ascontiguousarray(test_points, dtype=float)
+    if points.ndim != 2 or test_points.ndim != 2:
+        raise ValueError('points and test_points must be 2D arrays (num_points, dimension)')
+    if points.shape[1] != test_points.shape[1]:
+        raise ValueError('test_points have dimension %d, points %d'
+                         % (test_points.shape[1], points.shape[1]))
+    scale = _broadcast_scale(points, correlation_scale)
+    return _hip.matern_cross(test_points, points, scale, nu, device=device)

@@ -129,6 +129,44 @@ int gpmi_op_last_timing(gpmi_op* op, double* syrk_ms, int* syrk_launches,
  * default 16); each outer panel is factorized recursively (halves). */
 int gpmi_op_set_outer(gpmi_op* op, int s);
 
+/* ------------------------------------------------------------- prediction --
+ * The reference stops at training (its GaussianProcess has no predict); these
+ * entry points serve gaussian_proc.GaussianProcess.predict of this build. */
+
+/* Matérn cross-correlation of two point sets, host in / host out: the
+ * counterpart of gpmi_matern_dense. points: [n][d], test_points: [nstar][d],
+ * C_out[j][i] = matern(test_j, points_i), [nstar][ldc]. A test point equal to a
+ * training point gives bit for bit the entry gpmi_matern_dense produces. */
+int gpmi_matern_cross(int device, const double* points, int64_t n,
+                      const double* test_points, int64_t nstar, int d,
+                      const double* scale, double nu, double* C_out, int64_t ldc);
+
+/* Prediction terms at nstar new points from the cached factor of
+ * K + eta I = L L^T (factorized if absent) and the resident RHS block R of
+ * gpmi_op_set_rhs. With k*_j the correlations of test point j with the n training
+ * points, v_j = L^-1 k*_j and Y = L^-1 R:
+ *   c_out[nstar][nrhs]    c_j = Y^T v_j = R^T (K + eta I)^-1 k*_j
+ *   q_out[nstar]          q_j = v_j^T v_j = k*_j^T (K + eta I)^-1 k*_j
+ *   gram_out[nrhs][nrhs]  Y^T Y = R^T (K + eta I)^-1 R
+ * (any may be NULL). k* is assembled on the device from points [n][d] (the points
+ * K was assembled from), scale [d], nu and test_points [nstar][d]; or, when
+ * kstar != NULL, uploaded from the host block kstar[nstar][ldks] (a K that did not
+ * come from this library's Matérn; points, scale, test_points may then be NULL).
+ * A wide forward substitution on fp64 MFMA in chunks of test columns; the solved
+ * block never leaves the device. The environment variable GPMI_PREDICT_CHUNK
+ * (columns, a multiple of 128) overrides the chunk width.
+ * > 0: first non-positive pivot; < 0: null handle, no resident RHS, d outside
+ * 1..8 (device assembly), nstar < 1. */
+int gpmi_op_predict_terms(gpmi_op* op, double eta, const double* points, int d,
+                          const double* scale, double nu, const double* test_points,
+                          int64_t nstar, const double* kstar, int64_t ldks,
+                          double* c_out, double* q_out, double* gram_out);
+
+/* HIP-event timing of the last gpmi_op_predict_terms when gpmi_op_set_timing is
+ * on: the whole call, the trailing products' total device ms and their flops. */
+int gpmi_op_predict_ms(gpmi_op* op, double* total_ms, double* trailing_ms,
+                       double* trailing_flops);
+
 /* ------------------------------------------------------------------ sparse --
  * Tapered (compact-support) Matérn correlation in CSR on the device, and the
  * Krylov primitives of the sparse likelihood path. Replaces
