@@ -97,7 +97,17 @@ struct gpmi_op {
   double* Ppart = nullptr;   // [nt][wide][17] per-tile-row partials
   double* Pout = nullptr;    // [wide][17]
   double* Pgram = nullptr;   // [nt][256] partials, then [256] G = Y^T Y
-  int pred_wide = 0;         // columns the workspace holds
+  int pred_wide = 0;         // columns Ppart / Pout hold
+  int64_t pred_t_rows = 0;   // rows PT holds (= pred_wide until a covariance call widens it)
+  // joint covariance (gpmi_op_predict_cov): PT then holds every test column
+  double* Pcov = nullptr;    // [nsp][nsp] K**, then C0 = K** - V V^T
+  double* Pcpart = nullptr;  // [tiles][S][128][128] depth pieces of the product
+  int64_t pred_cov_rows = 0; // nsp Pcov holds
+  size_t pred_cpart = 0;     // doubles Pcpart holds
+  int ncu = 0;               // compute units (read at the first covariance call)
+  hipEvent_t cov_ev[2] = {nullptr, nullptr};
+  double last_cov_ms = 0.0, last_cov_flops = 0.0;
+  int last_cov_split = 0;    // depth pieces of the last covariance call
   uint64_t rhs_gen = 0;      // bumped by gpmi_op_set_rhs
   uint64_t ry_gen = ~0ull;   // factor generation for which R slot 0 holds L^-1 rhs_src
   uint64_t ry_rhs = ~0ull;   // ... and the rhs generation
@@ -664,7 +674,8 @@ int gpmi_op_destroy(gpmi_op* op) {
   if (op->stream3) (void)hipStreamSynchronize(op->stream3);
   double* bufs[] = {op->K, op->A, op->R, op->X, op->U, op->Linv, op->logdiag, op->gram,
                     op->out, op->etas, op->rhs_src, op->scratch, op->scratch2, op->tracebuf,
-                    op->W, op->tpart, op->Td, op->PY, op->PT, op->Ppart, op->Pout, op->Pgram};
+                    op->W, op->tpart, op->Td, op->PY, op->PT, op->Ppart, op->Pout, op->Pgram,
+                    op->Pcov, op->Pcpart};
   for (double* p : bufs)
     if (p) (void)hipFree(p);
   if (op->info) (void)hipFree(op->info);
@@ -672,6 +683,8 @@ int gpmi_op_destroy(gpmi_op* op) {
   for (auto e : op->ev) (void)hipEventDestroy(e);
   for (auto e : op->colpanel_ev) (void)hipEventDestroy(e);
   for (auto e : op->pred_ev) (void)hipEventDestroy(e);
+  for (auto e : op->cov_ev)
+    if (e) (void)hipEventDestroy(e);
   if (op->ev_begin) (void)hipEventDestroy(op->ev_begin);
   if (op->ev_end) (void)hipEventDestroy(op->ev_end);
   if (op->ev_fork) (void)hipEventDestroy(op->ev_fork);
@@ -1058,10 +1071,21 @@ static int predict_refresh_y(gpmi_op* op) {
   return 0;
 }
 
-int gpmi_op_predict_terms(gpmi_op* op, double eta, const double* points, int d,
-                          const double* scale, double nu, const double* test_points,
-                          int64_t nstar, const double* kstar, int64_t ldks, double* c_out,
-                          double* q_out, double* gram_out) {
+// The joint-covariance request of gpmi_op_predict_cov (none: gpmi_op_predict_terms).
+struct PredictCov {
+  const double* kss;
+  int64_t ldkss;
+  double* out;
+  int64_t ldcov;
+};
+
+// gpmi_op_predict_terms and gpmi_op_predict_cov. Without `cov` the working block holds
+// one chunk at a time; with it every chunk keeps its rows of the whole block, and
+// C0 = K** - V V^T follows the chunks.
+static int predict_run(gpmi_op* op, double eta, const double* points, int d,
+                       const double* scale, double nu, const double* test_points,
+                       int64_t nstar, const double* kstar, int64_t ldks, double* c_out,
+                       double* q_out, double* gram_out, const PredictCov* cov) {
   if (!op) return set_err(-1006, "null handle");
   if (!op->has_K) return set_err(-1000, "operator has no matrix (load or assemble first)");
   if (op->nrhs < 1) return set_err(-1012, "no resident right-hand sides (gpmi_op_set_rhs)");
@@ -1076,6 +1100,17 @@ int gpmi_op_predict_terms(gpmi_op* op, double eta, const double* points, int d,
   } else if (ldks < op->n) {
     return set_err(-1014, "ldks %lld below n = %lld", (long long)ldks, (long long)op->n);
   }
+  if (cov) {
+    if (!cov->out) return set_err(-1004, "null argument");
+    if (cov->ldcov < nstar)
+      return set_err(-1016, "ldcov %lld below nstar = %lld", (long long)cov->ldcov,
+                     (long long)nstar);
+    if (kstar && !cov->kss)
+      return set_err(-1017, "an uploaded kstar needs kss, the test points' own correlations");
+    if (kstar && cov->ldkss < nstar)
+      return set_err(-1018, "ldkss %lld below nstar = %lld", (long long)cov->ldkss,
+                     (long long)nstar);
+  }
   int64_t knob = 0;   // GPMI_PREDICT_CHUNK: the chunk width in columns (read per call)
   if (const char* e = std::getenv("GPMI_PREDICT_CHUNK"))
     if (*e) knob = std::atoll(e) > 0 ? std::atoll(e) : -1;
@@ -1085,6 +1120,24 @@ int gpmi_op_predict_terms(gpmi_op* op, double eta, const double* points, int d,
   if (NS < 0) return set_err(-1015, "GPMI_PREDICT_CHUNK must be a positive multiple of 128");
   DeviceGuard g(op->device);
   hipStream_t s = op->stream;
+  // covariance: column tiles of the whole block, the depth split, and the cap
+  const int64_t nsp = (nstar + TS - 1) / TS * TS;
+  int cnct = 0, csplit = 1;
+  if (cov) {
+    cnct = (int)std::min<int64_t>(nsp / TS, 1 << 20);   // (beyond: over the cap in any case)
+    if (!op->ncu)
+      HIP_TRY(hipDeviceGetAttribute(&op->ncu, hipDeviceAttributeMultiprocessorCount,
+                                    op->device));
+    int64_t sknob = 0;   // GPMI_PREDICT_COV_SPLIT: the number of depth pieces (read per call)
+    if (const char* e = std::getenv("GPMI_PREDICT_COV_SPLIT"))
+      if (*e) sknob = std::atoll(e);
+    csplit = predict_cov_split(predict_cov_tiles(cnct), nt, 2 * op->ncu, sknob);
+    if (!predict_cov_fits(np, cnct, csplit))
+      return set_err(-1019,
+                     "covariance of %lld points at n_pad %lld, split %d is over the %lld MiB cap",
+                     (long long)nstar, (long long)np, csplit,
+                     (long long)(PRED_COV_BYTES >> 20));
+  }
   bool fresh;
   int rc = ensure_factor(op, eta, op->rhs_src, &fresh);
   if (rc) return rc;
@@ -1101,17 +1154,49 @@ int gpmi_op_predict_terms(gpmi_op* op, double eta, const double* points, int d,
     HIP_TRY(hipMalloc(&op->PY, sizeof(double) * (size_t)np * RLD));
     HIP_TRY(hipMalloc(&op->Pgram, sizeof(double) * (size_t)(nt + 1) * 256));
   }
-  if (op->pred_wide < wide) {
+  const int64_t t_rows = cov ? nsp : wide;   // PT: one chunk, or every test column
+  if (op->pred_wide < wide || op->pred_t_rows < t_rows) {
     const PredictSizes sz = predict_sizes(np, nt, wide);
-    for (double** p : {&op->PT, &op->Ppart, &op->Pout}) {
-      if (*p) HIP_TRY(hipFree(*p));
-      *p = nullptr;
+    if (op->pred_t_rows < t_rows) {
+      if (op->PT) HIP_TRY(hipFree(op->PT));
+      op->PT = nullptr;
+      op->pred_t_rows = 0;
     }
-    op->pred_wide = 0;
-    HIP_TRY(hipMalloc(&op->PT, sizeof(double) * sz.T));
-    HIP_TRY(hipMalloc(&op->Ppart, sizeof(double) * sz.part));
-    HIP_TRY(hipMalloc(&op->Pout, sizeof(double) * sz.out));
-    op->pred_wide = wide;
+    if (op->pred_wide < wide) {
+      for (double** p : {&op->Ppart, &op->Pout}) {
+        if (*p) HIP_TRY(hipFree(*p));
+        *p = nullptr;
+      }
+      op->pred_wide = 0;
+    }
+    if (!op->PT) {
+      HIP_TRY(hipMalloc(&op->PT, sizeof(double) * (size_t)t_rows * (size_t)np));
+      op->pred_t_rows = t_rows;
+    }
+    if (!op->Ppart) {
+      HIP_TRY(hipMalloc(&op->Ppart, sizeof(double) * sz.part));
+      HIP_TRY(hipMalloc(&op->Pout, sizeof(double) * sz.out));
+      op->pred_wide = wide;
+    }
+  }
+  if (cov) {
+    const PredictCovSizes cz = predict_cov_sizes(np, cnct, csplit);
+    if (op->pred_cov_rows < nsp) {
+      if (op->Pcov) HIP_TRY(hipFree(op->Pcov));
+      op->Pcov = nullptr;
+      op->pred_cov_rows = 0;
+      HIP_TRY(hipMalloc(&op->Pcov, sizeof(double) * cz.cov));
+      op->pred_cov_rows = nsp;
+    }
+    if (op->pred_cpart < cz.part) {
+      if (op->Pcpart) HIP_TRY(hipFree(op->Pcpart));
+      op->Pcpart = nullptr;
+      op->pred_cpart = 0;
+      HIP_TRY(hipMalloc(&op->Pcpart, sizeof(double) * cz.part));
+      op->pred_cpart = cz.part;
+    }
+    if (op->timing && !op->cov_ev[0])
+      for (hipEvent_t& e : op->cov_ev) HIP_TRY(hipEventCreateWithFlags(&e, timing_event_flags()));
   }
   const std::vector<PredictLaunch> plan = predict_plan(nt, predict_outer(op->outer));
   size_t nev = 2;
@@ -1144,26 +1229,28 @@ int gpmi_op_predict_terms(gpmi_op* op, double eta, const double* points, int d,
   for (const PredictChunk& ch : chunks) {
     const int nct = ch.nct;
     const int64_t rows = (int64_t)nct * TS;   // rows of T this chunk runs (<= wide)
+    // the chunk's rows: the block itself, or its range of the whole block
+    double* const PTc = op->PT + (cov ? predict_cov_row0(ch) * np : 0);
     if (kstar) {
-      HIP_TRY(hipMemsetAsync(op->PT, 0, sizeof(double) * rows * np, s));
-      HIP_TRY(hipMemcpy2DAsync(op->PT, sizeof(double) * np, kstar + ch.j0 * ldks,
+      HIP_TRY(hipMemsetAsync(PTc, 0, sizeof(double) * rows * np, s));
+      HIP_TRY(hipMemcpy2DAsync(PTc, sizeof(double) * np, kstar + ch.j0 * ldks,
                                sizeof(double) * ldks, sizeof(double) * n, ch.cols,
                                hipMemcpyHostToDevice, s));
     } else {
       launch_matern_cross(s, dp, n, static_cast<double*>(dt) + ch.j0 * d, ch.cols, d, ds, MP,
-                          op->PT, np, rows, np);
+                          PTc, np, rows, np);
       LAUNCH_CHECK("matern_cross_kernel");
     }
     for (const PredictLaunch& L : plan) {
       if (L.kind == PRED_DIAG) {
         hipLaunchKernelGGL(pred_diag_kernel, dim3(nct), dim3(256), 0, s, op->A, np, op->Linv,
-                           op->PY, op->PT, np, L.r0, L.kb, op->Ppart, rows);
+                           op->PY, PTc, np, L.r0, L.kb, op->Ppart, rows);
         LAUNCH_CHECK("pred_diag_kernel");
       } else {
         const int ni = L.r1 - L.r0;
         if (op->timing) HIP_TRY(hipEventRecord(op->pred_ev[evi++], s));
         hipLaunchKernelGGL(pred_update_kernel, dim3(ni * nct), dim3(256), 0, s, op->A, np,
-                           op->PT, np, L.r0, ni, nct, L.kb, L.ke);
+                           PTc, np, L.r0, ni, nct, L.kb, L.ke);
         LAUNCH_CHECK("pred_update_kernel");
         if (op->timing) HIP_TRY(hipEventRecord(op->pred_ev[evi++], s));
         trail_flops += 2.0 * TS * TS * (double)(L.ke - L.kb) * TS * ni * nct;
@@ -1189,6 +1276,40 @@ int gpmi_op_predict_terms(gpmi_op* op, double eta, const double* points, int d,
     for (int a = 0; a < m; ++a)
       for (int c = 0; c < m; ++c) gram_out[a * m + c] = hg[a * RLD + c];
   }
+  if (cov) {
+    // K** into Pcov [nsp][nsp] (pad rows / columns zero), then C0 in place
+    const int64_t ldc = op->pred_cov_rows;
+    if (kstar) {
+      HIP_TRY(hipMemsetAsync(op->Pcov, 0, sizeof(double) * nsp * ldc, s));
+      HIP_TRY(hipMemcpy2DAsync(op->Pcov, sizeof(double) * ldc, cov->kss,
+                               sizeof(double) * cov->ldkss, sizeof(double) * nstar, nstar,
+                               hipMemcpyHostToDevice, s));
+    } else {
+      launch_matern_cross(s, dt, nstar, dt, nstar, d, ds, MP, op->Pcov, ldc, nsp, nsp);
+      LAUNCH_CHECK("matern_cross_kernel");
+    }
+    const int ntiles = (int)predict_cov_tiles(cnct);
+    if (op->timing) HIP_TRY(hipEventRecord(op->cov_ev[0], s));
+    hipLaunchKernelGGL(pred_cov_partial_kernel, dim3((unsigned)(ntiles * csplit)), dim3(256), 0,
+                       s, op->PT, np, cnct, nt, csplit, op->Pcpart);
+    LAUNCH_CHECK("pred_cov_partial_kernel");
+    if (op->timing) HIP_TRY(hipEventRecord(op->cov_ev[1], s));
+    hipLaunchKernelGGL(pred_cov_reduce_kernel, dim3(ntiles, TS / 16), dim3(256), 0, s,
+                       op->Pcpart, csplit, cnct, op->Pcov, ldc);
+    LAUNCH_CHECK("pred_cov_reduce_kernel");
+    HIP_TRY(hipMemcpy2DAsync(cov->out, sizeof(double) * cov->ldcov, op->Pcov,
+                             sizeof(double) * ldc, sizeof(double) * nstar, nstar,
+                             hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    op->last_cov_ms = op->last_cov_flops = 0.0;
+    op->last_cov_split = csplit;
+    if (op->timing) {
+      float ms = 0.f;
+      HIP_TRY(hipEventElapsedTime(&ms, op->cov_ev[0], op->cov_ev[1]));
+      op->last_cov_ms = ms;
+      op->last_cov_flops = 2.0 * TS * TS * (double)np * ntiles;
+    }
+  }
   op->last_pred_ms = op->last_pred_trail_ms = op->last_pred_trail_flops = 0.0;
   if (op->timing) {
     HIP_TRY(hipEventRecord(op->pred_ev[1], s));
@@ -1204,6 +1325,37 @@ int gpmi_op_predict_terms(gpmi_op* op, double eta, const double* points, int d,
     op->last_pred_trail_ms = tr;
     op->last_pred_trail_flops = trail_flops;
   }
+  return 0;
+}
+
+int gpmi_op_predict_terms(gpmi_op* op, double eta, const double* points, int d,
+                          const double* scale, double nu, const double* test_points,
+                          int64_t nstar, const double* kstar, int64_t ldks, double* c_out,
+                          double* q_out, double* gram_out) {
+  return predict_run(op, eta, points, d, scale, nu, test_points, nstar, kstar, ldks, c_out,
+                     q_out, gram_out, nullptr);
+}
+
+int gpmi_op_predict_cov(gpmi_op* op, double eta, const double* points, int d,
+                        const double* scale, double nu, const double* test_points,
+                        int64_t nstar, const double* kstar, int64_t ldks, const double* kss,
+                        int64_t ldkss, double* c_out, double* q_out, double* gram_out,
+                        double* cov_out, int64_t ldcov) {
+  const PredictCov cov = {kss, ldkss, cov_out, ldcov};
+  return predict_run(op, eta, points, d, scale, nu, test_points, nstar, kstar, ldks, c_out,
+                     q_out, gram_out, &cov);
+}
+
+int gpmi_op_predict_cov_ms(gpmi_op* op, double* product_ms, double* product_flops) {
+  if (!op) return set_err(-1006, "null handle");
+  if (product_ms) *product_ms = op->last_cov_ms;
+  if (product_flops) *product_flops = op->last_cov_flops;
+  return 0;
+}
+
+int gpmi_op_predict_cov_split(gpmi_op* op, int* split) {
+  if (!op) return set_err(-1006, "null handle");
+  if (split) *split = op->last_cov_split;
   return 0;
 }
 

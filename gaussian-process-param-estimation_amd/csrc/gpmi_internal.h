@@ -102,6 +102,10 @@ __global__ void pred_diag_kernel(const double* L, int64_t lda, const double* Lin
                                  double* part, int64_t ns_ld);
 __global__ void pred_reduce_kernel(const double* part, int nt, int64_t cnt, double* out);
 __global__ void pred_gram_kernel(const double* Y, double* gpart);
+__global__ void pred_cov_partial_kernel(const double* T, int64_t ldt, int nct, int nt, int S,
+                                        double* part);
+__global__ void pred_cov_reduce_kernel(const double* part, int S, int nct, double* C,
+                                       int64_t ldc);
 
 // Multi-shift CG Gram state (gpmi_sparse.hip, gpmi_sparse_api.hip); device pointers.
 #ifndef GPMI_LZ_JC

@@ -22,6 +22,11 @@
 //   pred_gram_kernel    per tile row, Y_k^T Y_k (16 x 16) -> summed by pred_reduce_kernel
 // Rows i >= n of T are zero and L's pad is the identity, so V's pad rows stay zero and
 // contribute nothing.
+//
+// The joint covariance (gpmi_op_predict_cov) keeps every chunk's rows of T, so that V^T for
+// all test points is one [nsp][ldt] block, and forms C0 = K** - V V^T from it:
+//   pred_cov_partial_kernel  one (lower tile, depth piece) per workgroup, -T_J T_L^T
+//   pred_cov_reduce_kernel   K** + the pieces in ascending order, stored with its mirror
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -223,6 +228,77 @@ __global__ __launch_bounds__(256) void pred_gram_kernel(const double* __restrict
   double s = 0.0;
   for (int r = 0; r < TS; ++r) s = fma(sY[r * RLD + a], sY[r * RLD + c], s);
   gpart[(int64_t)k * 256 + t] = s;
+}
+
+// Joint covariance C0 = K** - V V^T of the test points, V^T = T [nsp][ldt] whole
+// (every chunk's rows kept). Grid: ntiles * S workgroups, ntiles = nct (nct + 1) / 2
+// lower tiles (J, L), J >= L, by tri_decode; workgroup q = piece * ntiles + tile, so
+// the workgroups in flight on one XCD (xcd_remap) run consecutive tiles of one depth
+// piece and share its row slabs in L2. Piece p covers the tile rows
+// [p nt / S, (p + 1) nt / S) (predict_cov_piece_begin). Both operands are [row][k] slabs
+// of T; the partial, -T_J,[k0,k1) T_L,[k0,k1)^T from zero accumulators, goes to
+// part[tile][p][128][128]. Reads T only; each workgroup writes its own partial tile.
+__global__ __launch_bounds__(256, 2) void pred_cov_partial_kernel(const double* __restrict__ T,
+                                                                  int64_t ldt, int nct, int nt,
+                                                                  int S,
+                                                                  double* __restrict__ part) {
+  __shared__ double smem[4 * STAGE];
+  const int ntiles = nct * (nct + 1) / 2;
+  const int q = xcd_remap(blockIdx.x, gridDim.x);
+  const int p = q / ntiles, tile = q - p * ntiles;
+  int J, L;
+  tri_decode(tile, nct, &J, &L);
+  const int k0 = predict_cov_piece_begin(nt, S, p), k1 = predict_cov_piece_begin(nt, S, p + 1);
+  d4 acc[4][4];
+#pragma unroll
+  for (int a = 0; a < 4; ++a)
+#pragma unroll
+    for (int c = 0; c < 4; ++c) acc[a][c] = d4{0.0, 0.0, 0.0, 0.0};
+  d4 dummy[2];
+  tile_mma<false, true>(T + (int64_t)J * TS * ldt + (int64_t)k0 * TS, ldt,
+                        T + (int64_t)L * TS * ldt + (int64_t)k0 * TS, ldt, (k1 - k0) * TS, smem,
+                        smem + 2 * STAGE, acc, nullptr, dummy);
+  store_c(part + predict_cov_part_off(tile, S, p), TS, acc);
+}
+
+// C tile (J, L) = K**_JL + sum_p part[tile][p], p ascending, in place in C [nsp][ldc]
+// (which holds K** on entry), stored as tile (J, L) and transposed as tile (L, J). Only
+// the lower tiles of K**, and of a diagonal tile only the entries r >= c, are read, and
+// what is written besides is read by nobody: C comes out exactly symmetric whatever the
+// upper half held. Grid: (ntiles, 8), a workgroup takes 16 rows of its tile; the
+// transposed store goes through LDS so that 16 lanes write one 128-B row segment.
+__global__ __launch_bounds__(256) void pred_cov_reduce_kernel(const double* __restrict__ part,
+                                                              int S, int nct, double* C,
+                                                              int64_t ldc) {
+  __shared__ double sm[16][TS + 1];
+  int J, L;
+  tri_decode((int)blockIdx.x, nct, &J, &L);
+  const int t = threadIdx.x, r0 = blockIdx.y * 16;
+  const bool diag = J == L;
+  const double* pt = part + predict_cov_part_off(blockIdx.x, S, 0);
+  double* Cjl = C + (int64_t)J * TS * ldc + (int64_t)L * TS;
+  {
+    const int c = t & (TS - 1);
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int rl = (t >> 7) + 2 * i, r = r0 + rl;
+      if (!diag || r >= c) {
+        double s = 0.0;
+        for (int p = 0; p < S; ++p) s += pt[(int64_t)p * TS * TS + r * TS + c];
+        const double v = Cjl[(int64_t)r * ldc + c] + s;
+        Cjl[(int64_t)r * ldc + c] = v;
+        sm[rl][c] = v;
+      }
+    }
+  }
+  __syncthreads();
+  double* Clj = C + (int64_t)L * TS * ldc + (int64_t)J * TS;
+  const int rl = t & 15, r = r0 + rl;
+#pragma unroll
+  for (int i = 0; i < 8; ++i) {
+    const int c = (t >> 4) + 16 * i;
+    if (!diag || r > c) Clj[(int64_t)c * ldc + r] = sm[rl][c];
+  }
 }
 
 }  // namespace gpmi

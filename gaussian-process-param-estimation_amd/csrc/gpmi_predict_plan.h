@@ -122,6 +122,87 @@ GPMI_PLAN_HD inline void predict_tile(int q, int ni, int nct, int* pi, int* pj) 
   }
 }
 
+// ---------------------------------------------------------------------------
+// Joint covariance of the test points (gpmi_api.hip: gpmi_op_predict_cov; kernels
+// pred_cov_partial_kernel / pred_cov_reduce_kernel in gpmi_predict.hip):
+//   C0 = K** - V V^T,  V = L^-1 K*^T kept for ALL test points.
+// The working block is then the whole T [nsp][n_pad], nsp = n* rounded up to a tile;
+// the forward substitution still runs chunk by chunk on the row range of each chunk
+// (T is transposed: a chunk is a contiguous row range), part / out stay chunk-wide.
+// C0's lower tiles (J, L), J >= L, are SYRK-shaped products of depth n_pad; the depth is
+// split into S pieces of whole tile rows, one workgroup per (tile, piece) writing a
+// partial tile, summed in ascending piece order by the second kernel.
+// ---------------------------------------------------------------------------
+constexpr int64_t PRED_COV_BYTES = (int64_t)8 << 30;   // cap on T + K** + the partials
+
+// First row of a chunk's range inside the whole block (chunk widths are whole tiles).
+inline int64_t predict_cov_row0(const PredictChunk& ch) { return ch.j0; }
+
+inline int64_t predict_cov_tiles(int nct) { return (int64_t)nct * (nct + 1) / 2; }
+
+// Workspace in doubles: T [nsp][n_pad], cov [nsp][nsp], part [tiles][S][128][128].
+struct PredictCovSizes {
+  size_t T, cov, part;
+};
+
+inline PredictCovSizes predict_cov_sizes(int64_t n_pad, int nct, int S) {
+  const size_t nsp = (size_t)nct * PRED_TS;
+  return {nsp * (size_t)n_pad, nsp * nsp,
+          (size_t)predict_cov_tiles(nct) * (size_t)S * PRED_TS * PRED_TS};
+}
+
+// Whether a covariance call of nct column tiles at split S stays within the cap
+// (in tiles, so that no product overflows for any int nct).
+inline bool predict_cov_fits(int64_t n_pad, int nct, int S) {
+  const int64_t tile_bytes = (int64_t)8 * PRED_TS * PRED_TS;
+  const int64_t nt = n_pad / PRED_TS;
+  const int64_t tiles = (int64_t)nct * nt + (int64_t)nct * nct + predict_cov_tiles(nct) * S;
+  return tiles <= PRED_COV_BYTES / tile_bytes;
+}
+
+// Tile rows [begin(p), begin(p + 1)) of depth piece p of S, 1 <= S <= nt: balanced,
+// ragged where S does not divide nt, never empty.
+GPMI_PLAN_HD inline int predict_cov_piece_begin(int nt, int S, int p) {
+  return (int)((int64_t)p * nt / S);
+}
+
+// First double of the partial tile of (lower tile q, piece p).
+GPMI_PLAN_HD inline int64_t predict_cov_part_off(int64_t q, int S, int p) {
+  return (q * S + p) * (int64_t)(PRED_TS * PRED_TS);
+}
+
+// Number of depth pieces for `ntiles` lower tiles of depth nt tile rows on `slots`
+// resident workgroups (two per CU); `override_split` (GPMI_PREDICT_COV_SPLIT; <= 0:
+// none) replaces the choice, clipped to [1, nt]. In units of one 128^3 product per
+// slot the ntiles * S workgroups run ceil(ntiles S / slots) rounds of ceil(nt / S)
+// products, so (as symm_chunk, gpmi_band_plan.h) the S minimising rounds x depth ends
+// the grid in whole rounds; each partial tile adds a 128 KB write and read, about one
+// product's time per slot when all slots stream at once (128 KB x 2 at HBM rate / slots
+// against 2 x 128^3 flops at the fp64 MFMA rate / slots), counted as 1 / slots each.
+// Ties go to the smaller S. n* = 256, N = 16384: 3 tiles -> S = 128 (384 workgroups, one
+// round); n* = 4096: 528 tiles -> S = 8 (4224 workgroups, 8.25 rounds run as 9 of
+// depth 16: 144 + 8, against 2 rounds of depth 128 unsplit). Measured there, product ms
+// at S = 1 / 2 / 4 / 8 / 16 / 32: 6.40 / 5.30 / 4.82 / 4.61 / 4.43 / 4.61, the whole
+// call within 0.3 ms of each other from S = 2 on.
+inline int predict_cov_split(int64_t ntiles, int nt, int slots, int64_t override_split = 0) {
+  if (nt < 1) return 1;
+  if (override_split > 0) return (int)std::min<int64_t>(override_split, nt);
+  slots = std::max(slots, 1);
+  int best = 1;
+  double bc = -1.0;
+  for (int S = 1; S <= nt; ++S) {
+    const int64_t w = ntiles * S;
+    const int64_t rounds = (w + slots - 1) / slots;
+    const int depth = (nt + S - 1) / S;
+    const double c = (double)rounds * depth + (double)w / slots;
+    if (bc < 0.0 || c < bc) {
+      bc = c;
+      best = S;
+    }
+  }
+  return best;
+}
+
 }  // namespace gpmi
 
 #pragma GCC visibility pop

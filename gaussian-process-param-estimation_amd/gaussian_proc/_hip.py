@@ -62,6 +62,12 @@ SIGNATURES = {
                                              c_double_p, c_i64, c_double_p, c_double_p,
                                              c_double_p]),
     'gpmi_op_predict_ms': (ctypes.c_int, [c_op_p, c_double_p, c_double_p, c_double_p]),
+    'gpmi_op_predict_cov': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p, ctypes.c_int,
+                                           c_double_p, ctypes.c_double, c_double_p, c_i64,
+                                           c_double_p, c_i64, c_double_p, c_i64, c_double_p,
+                                           c_double_p, c_double_p, c_double_p, c_i64]),
+    'gpmi_op_predict_cov_ms': (ctypes.c_int, [c_op_p, c_double_p, c_double_p]),
+    'gpmi_op_predict_cov_split': (ctypes.c_int, [c_op_p, c_int_p]),
     'gpmi_last_assembly_ms': (ctypes.c_int, [c_double_p]),
     'gpmi_matern_values': (ctypes.c_int, [ctypes.c_int, c_double_p, c_i64, ctypes.c_double,
                                           c_double_p]),
@@ -373,6 +379,65 @@ class Operator(object):
         check(self.lib.gpmi_op_predict_terms(self.h, float(eta), *args, dptr(c), dptr(q),
                                              dptr(g)), 'gpmi_op_predict_terms')
         return c, q, g
+
+    def predict_cov(self, eta, test_points=None, points=None, scale=None, nu=None,
+                    cross=None, cross_star=None):
+        """-> (c, q, gram, C0): predict_terms' three, bit for bit, and
+        C0[nstar, nstar] = K** - K* (K + eta I)^-1 K*^T, exactly symmetric
+        (gpmi_op_predict_cov). K**, the correlations of the test points with each
+        other, is assembled on the device with k*, or, with the host matrix ``cross``
+        (nstar x n), taken from ``cross_star`` (nstar x nstar; its lower triangle is
+        read)."""
+        m = self.nrhs
+        if cross is not None:
+            cross = as_c(cross)
+            if cross.ndim != 2 or cross.shape[1] != self.n or cross.shape[0] < 1:
+                raise ValueError('cross must be nstar x %d with nstar >= 1' % self.n)
+            nstar = cross.shape[0]
+            if cross_star is None:
+                raise ValueError('cross needs cross_star, the nstar x nstar correlations of '
+                                 'the test points')
+            cross_star = as_c(cross_star)
+            if cross_star.shape != (nstar, nstar):
+                raise ValueError('cross_star must be %d x %d' % (nstar, nstar))
+            args = (None, 0, None, 0.0, None, nstar, dptr(cross), self.n, dptr(cross_star),
+                    nstar)
+        else:
+            if test_points is None or points is None or scale is None or nu is None:
+                raise ValueError('predict_cov needs test_points, points, scale and nu, '
+                                 'or cross and cross_star')
+            points = as_c(points)
+            test_points = as_c(test_points)
+            scale = as_c(scale)
+            if points.ndim != 2 or points.shape[0] != self.n:
+                raise ValueError('points must be %d x d' % self.n)
+            d = points.shape[1]
+            if test_points.ndim != 2 or test_points.shape[1] != d or test_points.shape[0] < 1:
+                raise ValueError('test_points must be nstar x %d with nstar >= 1' % d)
+            if scale.shape != (d,):
+                raise ValueError('scale must have one entry per dimension (%d)' % d)
+            nstar = test_points.shape[0]
+            args = (dptr(points), d, dptr(scale), float(nu), dptr(test_points), nstar, None, 0,
+                    None, 0)
+        c = numpy.empty((nstar, m))
+        q = numpy.empty(nstar)
+        g = numpy.empty((m, m))
+        cov = numpy.empty((nstar, nstar))
+        check(self.lib.gpmi_op_predict_cov(self.h, float(eta), *args, dptr(c), dptr(q), dptr(g),
+                                           dptr(cov), nstar), 'gpmi_op_predict_cov')
+        return c, q, g, cov
+
+    def predict_cov_ms(self):
+        """-> dict(product_ms, product_flops, split): the partial-product launch of the
+        last predict_cov with set_timing(True) (HIP events; 0 without), and the number
+        of depth pieces that call used."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        s = ctypes.c_int()
+        check(self.lib.gpmi_op_predict_cov_ms(self.h, ctypes.byref(a), ctypes.byref(b)),
+              'gpmi_op_predict_cov_ms')
+        check(self.lib.gpmi_op_predict_cov_split(self.h, ctypes.byref(s)),
+              'gpmi_op_predict_cov_split')
+        return dict(product_ms=a.value, product_flops=b.value, split=s.value)
 
     def predict_ms(self):
         """-> dict(total_ms, trailing_ms, trailing_flops) of the last predict_terms

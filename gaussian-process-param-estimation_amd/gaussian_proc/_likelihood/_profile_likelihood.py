@@ -96,6 +96,38 @@ def _predict_from_terms(c, q, G, Phi_star, sigma, sigma0, noise=False):
     return mean, var
 
 
+def _predict_cov_from_terms(c, G, C0, Phi_star, sigma, sigma0, noise=False):
+    """Joint posterior covariance of n* new points (universal kriging) from the
+    terms of MixedCorrelation.predict_cov_terms: c and G as in _predict_from_terms
+    and C0 = K** - K* S^-1 K*^T (n* x n*, symmetric). With B = G_XX and the rows
+    r_j = phi*_j - c_X,j,
+      cov = sigma^2 (C0 + r B^-1 r^T)          (the latent function; ``noise`` adds
+                                                sigma0^2 on the diagonal only)
+    whose diagonal is _predict_from_terms' variance. The rank-m term is symmetrised,
+    so cov is exactly symmetric when C0 is. m = 0 leaves cov = sigma^2 C0. -> cov."""
+    c = numpy.asarray(c, dtype=float)
+    G = numpy.asarray(G, dtype=float)
+    C0 = numpy.asarray(C0, dtype=float)
+    m = G.shape[0] - 1
+    if m < 0 or G.shape != (m + 1, m + 1) or c.ndim != 2 or c.shape[1] != m + 1 or \
+            C0.shape != (c.shape[0], c.shape[0]):
+        raise ValueError('c must be n* x (m + 1), G (m + 1) x (m + 1) and C0 n* x n*')
+    Phi = numpy.asarray(Phi_star, dtype=float).reshape(c.shape[0], -1)
+    if Phi.shape[1] != m:
+        raise ValueError('Phi_star must be n* x %d' % m)
+    if not sigma > 0.0:
+        raise ValueError('sigma must be positive')
+    cov = C0.copy()
+    if m > 0:
+        r = Phi - c[:, :m]
+        W = r @ numpy.linalg.solve(G[:m, :m], r.T)
+        cov += 0.5 * (W + W.T)
+    cov *= sigma ** 2
+    if noise:
+        cov[numpy.diag_indices_from(cov)] += sigma0 ** 2
+    return cov
+
+
 class ProfileLikelihood(object):
 
     @staticmethod

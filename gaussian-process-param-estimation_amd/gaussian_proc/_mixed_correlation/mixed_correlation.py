@@ -698,6 +698,37 @@ class MixedCorrelation(object):
         ``cross`` (n* x n), for a K that is not this package's Matérn. A sparse K
         raises NotImplementedError; K + eta I not positive definite raises
         numpy.linalg.LinAlgError. Returns (c, q, G)."""
+        test_points, points, correlation_scale, nu = self._predict_args(
+            X, test_points, cross, points, correlation_scale, nu, 'predict_terms')
+        self.set_rhs(X, z)
+        return self.op.predict_terms(eta, test_points=test_points, points=points,
+                                     scale=correlation_scale, nu=nu, cross=cross)
+
+    def predict_cov_terms(self, eta, X, z, test_points=None, cross=None, cross_star=None,
+                          points=None, correlation_scale=None, nu=None):
+        """predict_terms plus the joint covariance block of the n* new points:
+          C0[n*, n*] = K** - K* S^-1 K*^T,   S = K + eta I,
+        K** the correlations of the new points with each other. The solved block
+        V = L^-1 K*^T of predict_terms' forward substitution stays on the device for
+        all n* points and C0 = K** - V V^T is one split-depth SYRK on fp64 MFMA
+        (csrc/gpmi_predict.hip), exactly symmetric; _predict_cov_from_terms turns the
+        terms into the posterior covariance. Kernel parameters resolve as in
+        predict_terms; with ``cross`` (n* x n) the matrix ``cross_star`` (n* x n*) is
+        required (ValueError without). Returns (c, q, G, C0), the first three bit for
+        bit predict_terms'."""
+        test_points, points, correlation_scale, nu = self._predict_args(
+            X, test_points, cross, points, correlation_scale, nu, 'predict_cov_terms')
+        if cross is not None and cross_star is None:
+            raise ValueError('cross needs cross_star, the n* x n* correlations of the new '
+                             'points with each other')
+        self.set_rhs(X, z)
+        return self.op.predict_cov(eta, test_points=test_points, points=points,
+                                   scale=correlation_scale, nu=nu, cross=cross,
+                                   cross_star=cross_star)
+
+    def _predict_args(self, X, test_points, cross, points, correlation_scale, nu, who):
+        """The checks and kernel-parameter defaults predict_terms and
+        predict_cov_terms share -> (test_points, points, correlation_scale, nu)."""
         if self.sparse:
             raise NotImplementedError('prediction on a sparse K is not implemented')
         X = numpy.asarray(X, dtype=float)
@@ -705,7 +736,7 @@ class MixedCorrelation(object):
             raise ValueError('X must be %d x m' % self.n)
         if cross is None:
             if test_points is None:
-                raise ValueError('predict_terms needs test_points or cross')
+                raise ValueError('%s needs test_points or cross' % who)
             if isinstance(self.K, DeviceCorrelation):
                 points = self.K.points if points is None else points
                 correlation_scale = self.K.correlation_scale if correlation_scale is None \
@@ -726,9 +757,7 @@ class MixedCorrelation(object):
             if correlation_scale.size != points.shape[1]:
                 raise ValueError('correlation_scale must be a scalar or have one entry per '
                                  'dimension (%d)' % points.shape[1])
-        self.set_rhs(X, z)
-        return self.op.predict_terms(eta, test_points=test_points, points=points,
-                                     scale=correlation_scale, nu=nu, cross=cross)
+        return test_points, points, correlation_scale, nu
 
     def _exact_terms(self, etas):
         lds, gs = [], []

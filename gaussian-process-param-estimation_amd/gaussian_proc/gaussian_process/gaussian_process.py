@@ -5,7 +5,7 @@ the reference leaves as a commented-out stub."""
 import numpy
 
 from .._likelihood import Likelihood
-from .._likelihood._profile_likelihood import _predict_from_terms
+from .._likelihood._profile_likelihood import _predict_from_terms, _predict_cov_from_terms
 
 __all__ = ['GaussianProcess']
 
@@ -32,7 +32,7 @@ class GaussianProcess(object):
         self.results = results
 
     def predict(self, test_points, X_star, z=None, hyperparam=None, noise=False,
-                return_var=True, **kernel_params):
+                return_var=True, return_cov=False, **kernel_params):
         """Posterior mean (and variance) at ``test_points`` (n* x d) with basis rows
         ``X_star`` (n* x m): universal kriging with the fitted or given
         ``hyperparam = (sigma, sigma0)``,
@@ -44,7 +44,13 @@ class GaussianProcess(object):
         k* is assembled on the device from the kernel parameters of a
         DeviceCorrelation K; an ndarray K needs ``points``, ``correlation_scale``
         and ``nu`` (or ``cross``, the n* x n matrix itself) as keywords.
-        -> mean, or (mean, var) with ``return_var``."""
+        ``return_cov=True`` returns the joint posterior covariance (n* x n*, exactly
+        symmetric) in place of the variance,
+          cov = sigma^2 (K** - K* S^-1 K*^T + r (X^T S^-1 X)^-1 r^T),
+        ``noise=True`` adding sigma0^2 on its diagonal only; ``return_var`` is then
+        ignored, and ``cross`` needs ``cross_star``, the n* x n* correlations of the
+        new points with each other.
+        -> mean, (mean, var) with ``return_var``, or (mean, cov) with ``return_cov``."""
         if z is None:
             z = self.z
         if hyperparam is None and self.results is not None:
@@ -52,7 +58,8 @@ class GaussianProcess(object):
         if z is None or hyperparam is None:
             raise ValueError('predict needs z and hyperparam=(sigma, sigma0), or an earlier '
                              'train(z)')
-        bad = sorted(set(kernel_params) - {'points', 'correlation_scale', 'nu', 'cross'})
+        bad = sorted(set(kernel_params) - {'points', 'correlation_scale', 'nu', 'cross',
+                                           'cross_star'})
         if bad:
             raise TypeError('predict: unexpected keyword argument %s' % ', '.join(map(repr, bad)))
         sigma, sigma0 = float(hyperparam[0]), float(hyperparam[1])
@@ -69,7 +76,14 @@ class GaussianProcess(object):
         X_star = numpy.asarray(X_star, dtype=float)
         if X_star.shape != (test_points.shape[0], m):
             raise ValueError('X_star must be %d x %d' % (test_points.shape[0], m))
-        c, q, G = self.likelihood.K_mixed.predict_terms((sigma0 / sigma) ** 2, X, z,
-                                                        test_points=test_points, **kernel_params)
+        eta = (sigma0 / sigma) ** 2
+        if return_cov:
+            c, q, G, C0 = self.likelihood.K_mixed.predict_cov_terms(
+                eta, X, z, test_points=test_points, **kernel_params)
+            mean, _ = _predict_from_terms(c, q, G, X_star, sigma, sigma0, noise=noise)
+            return mean, _predict_cov_from_terms(c, G, C0, X_star, sigma, sigma0, noise=noise)
+        kernel_params.pop('cross_star', None)   # (only the covariance reads it)
+        c, q, G = self.likelihood.K_mixed.predict_terms(eta, X, z, test_points=test_points,
+                                                        **kernel_params)
         mean, var = _predict_from_terms(c, q, G, X_star, sigma, sigma0, noise=noise)
         return (mean, var) if return_var else mean

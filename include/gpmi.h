@@ -167,6 +167,34 @@ int gpmi_op_predict_terms(gpmi_op* op, double eta, const double* points, int d,
 int gpmi_op_predict_ms(gpmi_op* op, double* total_ms, double* trailing_ms,
                        double* trailing_flops);
 
+/* gpmi_op_predict_terms plus the joint covariance block of the nstar new points,
+ *   cov_out[nstar][ldcov]  C0 = K** - K* (K + eta I)^-1 K*^T = K** - V V^T,
+ * K** the correlations of the new points with each other and V = L^-1 K*^T, which
+ * this call keeps on the device for all nstar columns (the forward substitution
+ * still runs in chunks, on row ranges of the one block). C0 is a lower-tile SYRK
+ * on fp64 MFMA whose depth n_pad is split into S pieces, summed in ascending order
+ * without atomics: for a given S the result does not depend on the chunk width,
+ * and it is exactly symmetric. S is chosen from the tile count and the device's
+ * compute units; the environment variable GPMI_PREDICT_COV_SPLIT overrides it
+ * (read per call, clipped to n_pad / 128). K** is assembled on the device with k*,
+ * or, when kstar != NULL, uploaded from kss[nstar][ldkss] (only its lower triangle
+ * is read). c_out, q_out, gram_out are bit for bit those of gpmi_op_predict_terms
+ * and may be NULL; cov_out may not.
+ * > 0: first non-positive pivot; < 0: as gpmi_op_predict_terms, and ldcov < nstar,
+ * kstar without kss, ldkss < nstar, or a call whose working block, K** and
+ * partial products together exceed 8 GiB (nothing is allocated then). */
+int gpmi_op_predict_cov(gpmi_op* op, double eta, const double* points, int d,
+                        const double* scale, double nu, const double* test_points,
+                        int64_t nstar, const double* kstar, int64_t ldks,
+                        const double* kss, int64_t ldkss, double* c_out, double* q_out,
+                        double* gram_out, double* cov_out, int64_t ldcov);
+
+/* HIP-event timing of the partial-product launch of the last gpmi_op_predict_cov
+ * when gpmi_op_set_timing is on (device ms and flops; 0 otherwise), and the number
+ * of depth pieces S that call used. */
+int gpmi_op_predict_cov_ms(gpmi_op* op, double* product_ms, double* product_flops);
+int gpmi_op_predict_cov_split(gpmi_op* op, int* split);
+
 /* ------------------------------------------------------------------ sparse --
  * Tapered (compact-support) Matérn correlation in CSR on the device, and the
  * Krylov primitives of the sparse likelihood path. Replaces
