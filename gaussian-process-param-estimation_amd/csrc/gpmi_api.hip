@@ -51,6 +51,7 @@ struct gpmi_op {
   int max_batch = 1;
   int outer = 16;                      // outer panel width in 128-column tiles
   int panel_mode = DENSE_REC;          // schedule inside an outer panel (GPMI_PANEL)
+  int kloop = KLOOP_EARLY;             // k-loop form of syrk_kernel (GPMI_KLOOP)
   hipStream_t stream = nullptr;
   hipStream_t stream3 = nullptr;       // second batch group (groups == 2)
   int groups = 0;                      // 2: the batch runs as two halves on two streams;
@@ -189,7 +190,8 @@ int launch_syrk(gpmi_op* op, hipStream_t st, int b0, int nb, int tc0, int w, int
     auto it = op->order_off.find({w, t});
     if (it != op->order_off.end()) order = op->order + it->second;
   }
-  hipLaunchKernelGGL(syrk_kernel, dim3(tiles, nb), dim3(256), 0, st,
+  hipLaunchKernelGGL(op->kloop == KLOOP_LATE ? syrk_kernel<KLOOP_LATE> : syrk_kernel<KLOOP_EARLY>,
+                     dim3(tiles, nb), dim3(256), 0, st,
                      op->A + (int64_t)b0 * op->n_pad * op->n_pad, (int64_t)op->n_pad,
                      op->n_pad * op->n_pad, tc0, w, t, p0, kdim, order,
                      from_k ? op->K : nullptr, op->etas + b0, (int64_t)op->n);
@@ -622,6 +624,15 @@ int gpmi_op_create(int device, int64_t n, int max_batch, gpmi_op** out) {
     else if (std::strcmp(m, "rec") && *m) {
       delete op;
       return set_err(-1011, "GPMI_PANEL must be rec or col (got %s)", m);
+    }
+  }
+  if (const char* m = std::getenv("GPMI_KLOOP")) {
+    // early (the default): syrk_kernel's k-loop with the LDS hand-off off the MFMA path;
+    // late: the form before it (the bitwise tests and the in-process A/B). Same results.
+    if (!std::strcmp(m, "late")) op->kloop = KLOOP_LATE;
+    else if (std::strcmp(m, "early") && *m) {
+      delete op;
+      return set_err(-1009, "GPMI_KLOOP must be early or late (got %s)", m);
     }
   }
   op->trace = std::getenv("GPMI_SYRK_TRACE") != nullptr;

@@ -218,6 +218,8 @@ __global__ __launch_bounds__(256, 2) void colpanel_kernel(BatchPtrs P, int64_t l
 // Ksrc (the first trailing update of a factorization): C is read from the shared K
 // instead of the member's copy, with eta_b added on the diagonal of its first n rows,
 // so A_b = K + eta_b I is never copied for the tiles right of the first outer panel.
+// KL: the k-loop's pipeline form (gpmi_device.h), picked per operator (GPMI_KLOOP).
+template <int KL>
 __global__ __launch_bounds__(256, 2) void syrk_kernel(double* A, int64_t lda, int64_t sA,
                                                       int tc0, int w, int t, int p0,
                                                       int kdim, const uint32_t* order,
@@ -239,6 +241,11 @@ __global__ __launch_bounds__(256, 2) void syrk_kernel(double* A, int64_t lda, in
     tri_decode(q, w, &i, &j);
   }
   (void)t;
+  if (KL == KLOOP_EARLY) {
+    // the tile indices as scalars: the operand bases of gload_slab_u live in SGPRs
+    i = __builtin_amdgcn_readfirstlane(i);
+    j = __builtin_amdgcn_readfirstlane(j);
+  }
   const int I = tc0 + i, J = tc0 + j;
   double* Ab = A + blockIdx.y * sA;
   const double* P1 = Ab + (int64_t)I * TS * lda + p0;
@@ -260,9 +267,15 @@ __global__ __launch_bounds__(256, 2) void syrk_kernel(double* A, int64_t lda, in
         if (fk + 4 * r == fr && (int64_t)I * TS + wr * 64 + a * 16 + fr < n) acc[a][a][r] += eta;
   }
   d4 dummy[2];
-  tile_mma<false, true>(P1, lda, P2, lda, kdim, smem, smem + 2 * STAGE, acc, nullptr, dummy);
+  tile_mma<false, true, KL>(P1, lda, P2, lda, kdim, smem, smem + 2 * STAGE, acc, nullptr, dummy);
   store_c(C, lda, acc);
 }
+template __global__ void syrk_kernel<KLOOP_LATE>(double*, int64_t, int64_t, int, int, int, int,
+                                                 int, const uint32_t*, const double*,
+                                                 const double*, int64_t);
+template __global__ void syrk_kernel<KLOOP_EARLY>(double*, int64_t, int64_t, int, int, int, int,
+                                                  int, const uint32_t*, const double*,
+                                                  const double*, int64_t);
 
 // out[b][0] = logdet = sum of block partials; out[b][1 + e] = Gram entry e (16x16).
 __global__ __launch_bounds__(256) void finalize_kernel(BatchPtrs P, int nt, double* out,

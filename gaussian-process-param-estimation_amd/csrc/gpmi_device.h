@@ -74,16 +74,192 @@ __device__ __forceinline__ void sstore_slab(double* s, const d2 (&r)[4]) {
 }
 
 
+// gload_slab through a buffer descriptor: the address split as the hardware takes it, a
+// wave-uniform descriptor on the operand's base (base uniform), a scalar byte offset per
+// load (row block i, k offset p: SALU) and one 32-bit byte offset per thread,
+// slab_voff(ld). No 64-bit VALU add and no VGPR pair of address per load. Every offset
+// stays below 2^32 for ld < 2^22 (128 rows of 8 ld bytes).
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t slab_rsrc(const double* base) {
+  // raw buffer (stride 0), no range limit (the callers' tiles lie inside their matrices)
+  return __builtin_amdgcn_make_buffer_rsrc(const_cast<double*>(base), 0, 0xffffffff, 0x00020000);
+}
+__device__ __forceinline__ uint32_t slab_voff(int64_t ld) {
+  const int t = threadIdx.x;
+  return (uint32_t)(((t >> 3) * ld + 2 * (t & 7)) * 8);
+}
+__device__ __forceinline__ void gload_slab_u(__amdgpu_buffer_rsrc_t rs, int64_t ld, int p,
+                                             uint32_t voff, d2 (&r)[4]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    const uint32_t soff = (uint32_t)(((int64_t)(i * 32) * ld + p) * 8);
+    r[i] = __builtin_bit_cast(d2, __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0));
+  }
+}
+
+// The interleave of a stage of the KLOOP_EARLY form, pinned by sched_group_barrier
+// (masks: 0x8 MFMA, 0x100 DS read, 0x200 DS write). The scheduler left to itself issues
+// a k-step's fragment reads after its last MFMA, straight in front of the barrier's
+// lgkmcnt(0). N MFMAs, each followed by PER LDS instructions of the kind MASK:
+template <int MASK, int N, int PER>
+__device__ __forceinline__ void pin_behind_mfma() {
+#pragma unroll
+  for (int q = 0; q < N; ++q) {
+    __builtin_amdgcn_sched_group_barrier(0x8, 1, 0);
+    __builtin_amdgcn_sched_group_barrier(MASK, PER, 0);
+  }
+}
+// one k-step (16 MFMAs): LEAD MFMAs, the four fragment reads for the next k-step one
+// behind each of the next four MFMAs, then the rest.
+template <int LEAD>
+__device__ __forceinline__ void pin_kstep() {
+  if (LEAD > 0) __builtin_amdgcn_sched_group_barrier(0x8, LEAD, 0);
+  pin_behind_mfma<0x100, 4, 1>();
+  __builtin_amdgcn_sched_group_barrier(0x8, 12 - LEAD, 0);
+}
+
+// One stage (slab s, 16 k) of the KLOOP_EARLY form, the slab in buffer CUR. On entry
+// ra / rb hold slab s + 1, a / b the fragments of the stage's first k-step, and every
+// wave has passed the barrier E that ended stage s - 1. In program order:
+//   slab s + 1 goes from ra / rb to the other buffer behind the first four MFMAs, and the
+//   global loads of slab s + 2 follow into the same registers (has2; a uniform branch, the
+//   only one of the stage): a prefetch distance of two with one register set;
+//   the rest of k-step 0, k-step 1; barrier M; k-steps 2, 3, the last one reading the
+//   first fragments of stage s + 1 from the other buffer; barrier E.
+// Which barrier orders what:
+//   E (of stage s - 1) orders that stage's fragment reads of the other buffer, the
+//     pre-read of this stage's first fragments included, before the writes here (WAR);
+//   M orders the writes of slab s + 1 before its first fragment reads, the pre-read of
+//     k-step 3 (RAW). The writes were issued 28 MFMAs earlier, so the lgkmcnt(0) in front
+//     of M finds them done, and so does the one in front of E the pre-read (12 MFMAs);
+//   E (of this stage) also leaves the buffers free for the caller after the last stage.
+// No wave waits behind E for an LDS read: a and b are complete there. The last stage
+// runs the same code: it writes ra / rb (slab s, again) to the other buffer and reads
+// fragments from it that nothing uses.
+template <bool WITH_RHS, bool NEG, int CUR>
+__device__ __forceinline__ void tile_mma_early_stage(
+    __amdgpu_buffer_rsrc_t R1, int64_t ld1, __amdgpu_buffer_rsrc_t R2, int64_t ld2,
+    uint32_t vo1, uint32_t vo2, int s, bool has2, double* sA, double* sB, d4 (&acc)[4][4],
+    const double* sU, d4 (&racc)[2], d2 (&ra)[4], d2 (&rb)[4], double (&a)[4],
+    double (&b)[4]) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int wr = w >> 1, wc = w & 1;
+  const int fr = lane & 15, fk = lane >> 4;
+  const double* cA = sA + CUR * STAGE;
+  const double* cB = sB + CUR * STAGE;
+  double* nA = sA + (CUR ^ 1) * STAGE;
+  double* nB = sB + (CUR ^ 1) * STAGE;
+  sstore_slab(nA, ra);
+  sstore_slab(nB, rb);
+#pragma unroll
+  for (int kk = 0; kk < BK / 4; ++kk) {
+    double an[4], bn[4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (kk == 0 && i == 1) {
+        pin_behind_mfma<0x200, 4, 2>();
+        if (has2) {
+          gload_slab_u(R1, ld1, (s + 2) * BK, vo1, ra);
+          gload_slab_u(R2, ld2, (s + 2) * BK, vo2, rb);
+        }
+      }
+      if ((kk == 0 && i == 1) || (kk > 0 && i == 0)) {
+        // the next k-step's fragments (the next stage's first, after k-step 3)
+        const double* fA = kk + 1 < BK / 4 ? cA : nA;
+        const double* fB = kk + 1 < BK / 4 ? cB : nB;
+        const int kn = ((kk + 1) * 4) % BK + fk;
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) an[ii] = fA[slab_off(wr * 64 + ii * 16 + fr, kn)];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) bn[j] = fB[slab_off(wc * 64 + j * 16 + fr, kn)];
+      }
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        acc[i][j] = NEG ? mfma64_neg(a[i], b[j], acc[i][j]) : mfma64(a[i], b[j], acc[i][j]);
+    }
+    if (WITH_RHS) {
+      const double u = sU[(s * BK + kk * 4 + fk) * RLD + fr];
+      const double a0 = wc ? a[2] : a[0];
+      const double a1 = wc ? a[3] : a[1];
+      racc[0] = mfma64(a0, u, racc[0]);
+      racc[1] = mfma64(a1, u, racc[1]);
+    }
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      a[i] = an[i];
+      b[i] = bn[i];
+    }
+    if (kk == 1) {
+      // k-step 0's remaining 12 MFMAs (its reads behind the 9th to 12th), then k-step 1
+      __builtin_amdgcn_sched_group_barrier(0x8, 4, 0);
+      pin_behind_mfma<0x100, 4, 1>();
+      __builtin_amdgcn_sched_group_barrier(0x8, 4, 0);
+      pin_kstep<0>();
+      __builtin_amdgcn_sched_barrier(0);   // (every MFMA of k-steps 0, 1 ahead of M)
+      __syncthreads();                     // M
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+  pin_kstep<8>();
+  pin_kstep<0>();
+  __builtin_amdgcn_sched_barrier(0);   // (every MFMA of the stage ahead of E)
+  __syncthreads();                     // E
+  __builtin_amdgcn_sched_barrier(0);   // (no MFMA of the next stage moves up past E)
+}
+
+// kdim: a positive multiple of 2 BK (the stages run in pairs, so that the buffer parity,
+// and with it every LDS offset, is static).
+template <bool WITH_RHS, bool NEG>
+__device__ __forceinline__ void tile_mma_early(const double* __restrict__ P1, int64_t ld1,
+                                               const double* __restrict__ P2, int64_t ld2,
+                                               int kdim, double* sA, double* sB,
+                                               d4 (&acc)[4][4], const double* sU,
+                                               d4 (&racc)[2]) {
+  const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+  const int wr = w >> 1, wc = w & 1;
+  const int fr = lane & 15, fk = lane >> 4;
+  const int nsteps = kdim / BK;
+  const uint32_t vo1 = slab_voff(ld1), vo2 = slab_voff(ld2);
+  const __amdgpu_buffer_rsrc_t R1 = slab_rsrc(P1), R2 = slab_rsrc(P2);
+  d2 ra[4], rb[4];
+  gload_slab_u(R1, ld1, 0, vo1, ra);
+  gload_slab_u(R2, ld2, 0, vo2, rb);
+  sstore_slab(sA, ra);
+  sstore_slab(sB, rb);
+  // Drain every global load issued before the loop (the caller's accumulator preload)
+  // here, once, as the KLOOP_LATE form does, and before slab 1 is requested.
+  __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0) expcnt(7) lgkmcnt(15)
+  gload_slab_u(R1, ld1, BK, vo1, ra);
+  gload_slab_u(R2, ld2, BK, vo2, rb);
+  __syncthreads();   // slab 0 written -> its fragment reads
+  double a[4], b[4];
+#pragma unroll
+  for (int i = 0; i < 4; ++i) a[i] = sA[slab_off(wr * 64 + i * 16 + fr, fk)];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) b[j] = sB[slab_off(wc * 64 + j * 16 + fr, fk)];
+  __builtin_amdgcn_sched_barrier(0);
+  for (int s = 0; s < nsteps; s += 2) {
+    tile_mma_early_stage<WITH_RHS, NEG, 0>(R1, ld1, R2, ld2, vo1, vo2, s, s + 2 < nsteps, sA, sB,
+                                           acc, sU, racc, ra, rb, a, b);
+    tile_mma_early_stage<WITH_RHS, NEG, 1>(R1, ld1, R2, ld2, vo1, vo2, s + 1, s + 3 < nsteps, sA,
+                                           sB, acc, sU, racc, ra, rb, a, b);
+  }
+}
+
 // acc (wave tile 64 x 64 at (wr, wc)) += P1[0:128, 0:kdim] * P2[0:128, 0:kdim]^T.
 // f64 MFMA 16x16x4 operand maps: A[i = lane&15][k = lane>>4], B[k = lane>>4][j = lane&15].
 // WITH_RHS additionally accumulates racc (rows wr*64 + wc*32 + [0,32), 16 cols)
-// += P1 * U with U[kdim][16] staged in LDS.
-template <bool WITH_RHS, bool NEG = false>
+// += P1 * U with U[kdim][16] staged in LDS. KL: the k-loop's pipeline form (gpmi_internal.h;
+// KLOOP_EARLY needs wave-uniform P1 / P2 and kdim a multiple of 32). The same results either way.
+template <bool WITH_RHS, bool NEG = false, int KL = KLOOP_LATE>
 __device__ __forceinline__ void tile_mma(const double* __restrict__ P1, int64_t ld1,
                                          const double* __restrict__ P2, int64_t ld2,
                                          int kdim, double* sA, double* sB,
                                          d4 (&acc)[4][4], const double* sU,
                                          d4 (&racc)[2]) {
+  if constexpr (KL == KLOOP_EARLY) {
+    tile_mma_early<WITH_RHS, NEG>(P1, ld1, P2, ld2, kdim, sA, sB, acc, sU, racc);
+    return;
+  }
   const int t = threadIdx.x, lane = t & 63, w = t >> 6;
   const int wr = w >> 1, wc = w & 1;
   const int fr = lane & 15, fk = lane >> 4;

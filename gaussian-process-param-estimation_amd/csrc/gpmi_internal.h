@@ -68,6 +68,13 @@ __global__ void shift_copy_kernel(const double* K, int64_t ldk, double* A, int64
 __global__ void diag_block_kernel(BatchPtrs P, int64_t lda, int kb, int nt);
 __global__ void panel_kernel(BatchPtrs P, int64_t lda, int kb);
 __global__ void colpanel_kernel(BatchPtrs P, int64_t lda, int kb, int c0, int next_diag);
+// The two pipeline forms of tile_mma's k-loop (gpmi_device.h). Both run, per accumulator,
+// the same MFMA sequence in the same k order: the same results, bit for bit.
+//   KLOOP_LATE : the next slab's global loads at the start of a stage, its LDS writes
+//                after the stage's last MFMA, one barrier per stage.
+//   KLOOP_EARLY: the LDS hand-off off the MFMA path (tile_mma_early).
+enum { KLOOP_LATE = 0, KLOOP_EARLY = 1 };
+template <int KL>
 __global__ void syrk_kernel(double* A, int64_t lda, int64_t sA, int tc0, int w, int t,
                             int p0, int kdim, const uint32_t* order, const double* Ksrc,
                             const double* etas, int64_t n);

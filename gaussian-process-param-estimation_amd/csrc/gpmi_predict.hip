@@ -98,14 +98,17 @@ __global__ __launch_bounds__(256, 2) void pred_update_kernel(const double* __res
   const int q = xcd_remap(blockIdx.x, gridDim.x);
   int i, j;
   predict_tile(q, ni, nct, &i, &j);
-  i += i0;
+  // (the tile indices as scalars: the operand bases of the k-loop's slab loads live in SGPRs)
+  i = __builtin_amdgcn_readfirstlane(i) + i0;
+  j = __builtin_amdgcn_readfirstlane(j);
   double* rowJ = T + (int64_t)j * TS * ldt;
   double* C = rowJ + (int64_t)i * TS;
   d4 acc[4][4];
   load_c(C, ldt, acc);
   d4 dummy[2];
-  tile_mma<false, true>(rowJ + (int64_t)kb * TS, ldt, L + (int64_t)i * TS * lda + (int64_t)kb * TS,
-                        lda, (ke - kb) * TS, smem, smem + 2 * STAGE, acc, nullptr, dummy);
+  tile_mma<false, true, KLOOP_EARLY>(rowJ + (int64_t)kb * TS, ldt,
+                                     L + (int64_t)i * TS * lda + (int64_t)kb * TS, lda,
+                                     (ke - kb) * TS, smem, smem + 2 * STAGE, acc, nullptr, dummy);
   store_c(C, ldt, acc);
 }
 

@@ -38,8 +38,8 @@ print(json.dumps({'op': 'dpotrf (torch.linalg.cholesky)', 'n': n, 'ms': 1e3 * t,
                   'tflops': n ** 3 / 3.0 / t / 1e12}), flush=True)
 
 # The trailing-update shape of the blocked Cholesky: C (n x n) -= A_p B_p^T with a
-# k-panel of 512 / 1024 columns (outer panel of 4 / 8 tiles).
-for kd in (512, 1024):
+# k-panel of 512 / 1024 / 2048 columns (outer panel of 4 / 8 / 16 tiles).
+for kd in (512, 1024, 2048):
     P = torch.randn(n, kd, dtype=torch.float64, device=dev)
     C = torch.randn(n, n, dtype=torch.float64, device=dev)
     t = timed(lambda: C.addmm_(P, P.T, alpha=-1.0), 3)
