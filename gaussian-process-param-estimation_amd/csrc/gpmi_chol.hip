@@ -11,7 +11,7 @@
 // (_direct_likelihood.py:59,62,332); here one factorization serves all of them.
 //
 // Algorithm (lower, row-major A, 128-wide diagonal blocks, outer panels of
-// S sub-panels, see gpmi_api.hip): per sub-panel k
+// S sub-panels, see gpmi_dense_factor.hip): per sub-panel k
 //   diag_block_kernel : L_kk = chol(A_kk) in LDS, Linv_kk = L_kk^-1, logdet
 //                       partial, y_k = Linv_kk r_k, u_k = Linv_kk^T y_k, Gram y_k^T y_k
 //   panel_kernel      : L_ik = A_ik Linv_kk^T  and  r_i -= A_ik u_k  (= L_ik y_k)

@@ -1,4 +1,4 @@
-// Launch list of the dense blocked Cholesky (gpmi_api.hip: schedule): which kernel runs
+// Launch list of the dense blocked Cholesky (gpmi_dense_factor.hip: schedule): which kernel runs
 // on which tiles with which operand range, in stream order, for nt tile rows, outer
 // panels of `outer` tile columns and one of two panel schedules. Plain arithmetic, no
 // HIP here, so that the list is replayed on the host (tests/host/dense_plan_check.cpp).

@@ -1,6 +1,6 @@
-// Host-side helpers of the C-ABI translation units (gpmi_api.hip, gpmi_sparse_api.hip,
-// gpmi_band_*.hip): the HIP error checks, the device guard and an owner of a device
-// allocation.
+// Host-side helpers of the C-ABI translation units (gpmi_api.hip, gpmi_dense_*.hip,
+// gpmi_sparse_api.hip, gpmi_band_*.hip): the HIP error checks, the device guard and the
+// owners of device allocations, streams and events.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <initializer_list>
 #include <utility>
+#include <vector>
 
 namespace gpmi {
 
@@ -36,6 +37,9 @@ int set_error(int code, const char* msg);   // gpmi_api.hip: the thread's last e
 
 // (internal to the library: none of this is an exported symbol)
 #pragma GCC visibility push(hidden)
+
+// set_error with a printf-style message (gpmi_api.hip).
+int set_errorf(int code, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
 
 // Makes `dev` the current device for a scope.
 struct DeviceGuard {
@@ -102,13 +106,38 @@ struct Owned {
   Owned() = default;
   Owned(const Owned&) = delete;
   Owned& operator=(const Owned&) = delete;
-  ~Owned() {
-    if (h) (void)Destroy(h);
+  ~Owned() { (void)release(); }
+  // Destroys the handle now (none afterwards, until it is created again).
+  hipError_t release() {
+    hipError_t e = h ? Destroy(h) : hipSuccess;
+    h = nullptr;
+    return e;
   }
   operator H() const { return h; }
 };
 using Stream = Owned<hipStream_t, hipStreamDestroy>;
 using Event = Owned<hipEvent_t, hipEventDestroy>;
+
+// Events created on demand and kept: reserve(n, flags) makes [0, n) exist.
+struct EventPool {
+  std::vector<hipEvent_t> ev;
+  EventPool() = default;
+  EventPool(const EventPool&) = delete;
+  EventPool& operator=(const EventPool&) = delete;
+  ~EventPool() {
+    for (hipEvent_t e : ev) (void)hipEventDestroy(e);
+  }
+  hipError_t reserve(size_t n, unsigned flags) {
+    while (ev.size() < n) {
+      hipEvent_t e;
+      hipError_t rc = hipEventCreateWithFlags(&e, flags);
+      if (rc != hipSuccess) return rc;
+      ev.push_back(e);
+    }
+    return hipSuccess;
+  }
+  hipEvent_t operator[](size_t i) const { return ev[i]; }
+};
 
 // Buffers that share one capacity (in whatever unit the sizes were worked out for):
 // grown together to hold `want`. All of them are freed before the first is allocated

@@ -1,0 +1,164 @@
+// The dense operator's handle (include/gpmi.h, gpmi_op_*) and what its host translation
+// units share. One gpmi_op = one device-resident correlation matrix K (padded to n_pad,
+// a multiple of 128, identity in the pad) plus workspace for max_batch concurrent
+// factorizations of K + eta_b I. All work of an op runs in order on the op's own HIP
+// stream; the host blocks only when it reads results back. The handle is a core (K, the
+// resident RHS, the stream, the knobs) and one state per component:
+//   gpmi_api.hip            create / destroy, loading K, RHS, matvec, trace, the knobs
+//   gpmi_dense_factor.hip   the Cholesky schedule, its timing, and the calls that consume
+//                           a factor (DenseFactor, DenseTiming, DenseTraceInv)
+//   gpmi_dense_predict.hip  the prediction terms and the joint covariance (DensePredict)
+// Every device buffer is a DevBuf, every stream and event an owner (gpmi_host.h):
+// destruction is member order, streams after the buffers their work may touch.
+#pragma once
+
+#include <array>
+#include <map>
+#include <utility>
+#include <vector>
+
+#include "gpmi_internal.h"
+#include "gpmi_dense_plan.h"
+#include "gpmi_host.h"
+#include "../../include/gpmi.h"
+
+namespace gpmi {
+int matern_params_host(double nu, MaternParams* P);   // gpmi_api.hip
+}  // namespace gpmi
+
+#pragma GCC visibility push(hidden)
+
+namespace gpmi {
+
+constexpr int TS = GPMI_TS;
+constexpr int RLD = GPMI_RHS_LD;
+constexpr int OUT_LD = 1 + RLD * RLD;
+
+// The batch workspace of the factorization and the cached factor.
+struct DenseFactor {
+  Stream stream3;          // second batch group (groups == 2); alive only inside a
+                           // batched call (gpmi_op_loglik_batch releases it)
+  Event ev_fork, ev_g;     // stream -> stream3 at the start of the halves, and back
+  DevBuf<double> A;        // [max_batch][n_pad][n_pad]
+  DevBuf<double> R, X;     // [max_batch][n_pad][16] each
+  DevBuf<double> U;        // [max_batch][128][16]
+  DevBuf<double> Linv;     // [max_batch][nt][128][128]
+  DevBuf<double> logdiag;  // [max_batch][nt]
+  DevBuf<double> gram;     // [max_batch][nt][256]
+  DevBuf<double> out;      // [max_batch][OUT_LD]
+  DevBuf<double> etas;     // [max_batch]
+  DevBuf<int> info;        // [max_batch]
+  // grouped syrk tile orders, one per trailing-update shape (w, t) of the schedule
+  DevBuf<uint32_t> order;
+  int order_nt = -1, order_outer = -1, group = 8;
+  std::map<std::pair<int, int>, int64_t> order_off;
+  // factor cache: batch slot 0 holds the factor of K + cached_eta I
+  bool cache_valid = false;
+  double cached_eta = 0.0;
+
+  BatchPtrs ptrs(int64_t n_pad, int nt) const {
+    BatchPtrs p;
+    p.A = A, p.sA = n_pad * n_pad;
+    p.R = R, p.sR = n_pad * RLD;
+    p.U = U, p.sU = (int64_t)TS * RLD;
+    p.Linv = Linv, p.sL = (int64_t)nt * TS * TS;
+    p.logdiag = logdiag, p.sLD = nt;
+    p.gram = gram, p.sG = (int64_t)nt * 256;
+    p.info = info;
+    return p;
+  }
+};
+
+// HIP-event timing of the factorization and of the prediction (gpmi_op_set_timing).
+struct DenseTiming {
+  bool on = false;
+  bool trace = false;      // GPMI_SYRK_TRACE: per-class breakdown
+  EventPool span;          // begin, end of a factorization
+  EventPool syrk;          // (begin, end) per logged syrk_kernel launch
+  EventPool colpanel;      // (begin, end) per colpanel_kernel launch (trace only)
+  size_t colpanel_used = 0;
+  EventPool pred;          // begin, end of a prediction call; (begin, end) per trailing product
+  EventPool cov;           // begin, end of the covariance's partial-product launch
+  std::vector<std::pair<int, double>> syrk_log;  // (event index, flops)
+  std::vector<std::array<int, 3>> syrk_shape;    // (w, t, kdim) per logged launch
+  double last_syrk_ms = 0.0, last_syrk_flops = 0.0, last_total_ms = 0.0;
+  double last_syrk_busy_ms = 0.0;                // union of syrk launch intervals
+  int last_syrk_launches = 0;
+};
+
+// gpmi_op_traceinv: the workspace (allocated at the first call) and the trace cache.
+struct DenseTraceInv {
+  DevBuf<double> W;        // [n_pad][n_pad] L^-T
+  DevBuf<double> tpart;    // [nt * (nt + 1) / 2 + nt * nt] partials
+  DevBuf<double> Td;       // [nt][128][128] diagonal tiles of A^-1 (exponent 2)
+  uint64_t gen = ~0ull;    // the factor generation the cache is valid for
+  int have = 0;            // bit 0: tr(A^-1), bit 1: tr(A^-2)
+  double value[2] = {0.0, 0.0};
+};
+
+// gpmi_op_predict_terms / gpmi_op_predict_cov: workspace grown to the largest call so
+// far (sizes: gpmi_predict_plan.h), and where Y = L^-1 rhs_src currently is.
+struct DensePredict {
+  DevBuf<double> PY;       // [n_pad][16] Y, kept where solve does not write
+  DevBuf<double> Pgram;    // [nt][256] partials, then [256] G = Y^T Y
+  DevBuf<double> PT;       // [wide][n_pad] the chunk's working block, transposed; a
+                           // covariance call widens it to every test column
+  DevBuf<double> Ppart;    // [nt][wide][17] per-tile-row partials
+  DevBuf<double> Pout;     // [wide][17]
+  DevBuf<double> Pcov;     // [nsp][nsp] K**, then C0 = K** - V V^T
+  DevBuf<double> Pcpart;   // [tiles][S][128][128] depth pieces of the product
+  int ncu = 0;             // compute units (read at the first covariance call)
+  uint64_t ry_gen = ~0ull; // factor generation for which R slot 0 holds L^-1 rhs_src
+  uint64_t ry_rhs = ~0ull; // ... and the rhs generation
+  uint64_t py_gen = ~0ull, py_rhs = ~0ull;   // the same for PY / Pgram
+  double last_pred_ms = 0.0, last_pred_trail_ms = 0.0, last_pred_trail_flops = 0.0;
+  double last_cov_ms = 0.0, last_cov_flops = 0.0;
+  int last_cov_split = 0;  // depth pieces of the last covariance call
+};
+
+}  // namespace gpmi
+
+struct gpmi_op {
+  int device = 0;
+  int64_t n = 0, n_pad = 0;
+  int nt = 0;
+  int max_batch = 1;
+  int outer = 16;                      // outer panel width in 128-column tiles
+  int panel_mode = gpmi::DENSE_REC;    // schedule inside an outer panel (GPMI_PANEL)
+  int kloop = gpmi::KLOOP_EARLY;       // k-loop form of syrk_kernel (GPMI_KLOOP)
+  int groups = 0;                      // 2: the batch runs as two halves on two streams;
+                                       // 0: auto (2 for batches of 2..32, 1 above)
+  gpmi::Stream stream;
+  gpmi::DenseFactor fac;          // (here: its second stream, too, outlives the buffers below)
+  gpmi::DevBuf<double> K;         // [n_pad][n_pad]
+  gpmi::DevBuf<double> rhs_src;   // [n_pad][16] the resident RHS
+  gpmi::DevBuf<double> scratch;   // [n_pad][16] (matvec input, solve's RHS block)
+  gpmi::DevBuf<double> scratch2;  // [n_pad][16] (matvec output)
+  gpmi::DevBuf<double> tracebuf;  // [n_pad][2]
+  int nrhs = 0;
+  bool has_K = false;
+  uint64_t factor_gen = 0;        // bumped by every factorization
+  uint64_t rhs_gen = 0;           // bumped by gpmi_op_set_rhs
+  gpmi::DenseTiming tim;
+  gpmi::DenseTraceInv tinv;
+  gpmi::DensePredict pred;
+
+  gpmi::BatchPtrs ptrs() const { return fac.ptrs(n_pad, nt); }
+};
+
+namespace gpmi {
+
+// gpmi_api.hip: columns [col0, col0 + nrhs) of an [n][ld] host block into dst [n_pad][16]
+int upload_rhs(gpmi_op* op, double* dst, const double* rhs, int64_t ld, int nrhs, int col0);
+
+// gpmi_dense_factor.hip
+// The factor of K + eta I in batch slot 0, from the cache or by a factorization with
+// the fused forward substitution of rhs_dev (*fresh); read back as positive definite,
+// else the cache is dropped and the pivot is the error.
+int factor_ready(gpmi_op* op, double eta, const double* rhs_dev, bool* fresh);
+// R slot 0 <- L^-1 R slot 0 with the factor in slot 0.
+int forward_substitute(gpmi_op* op, const BatchPtrs& P);
+
+}  // namespace gpmi
+
+#pragma GCC visibility pop

@@ -1,4 +1,4 @@
-// Chunking, launch list and workspace sizes of the prediction terms (gpmi_api.hip:
+// Chunking, launch list and workspace sizes of the prediction terms (gpmi_dense_predict.hip:
 // gpmi_op_predict_terms; kernels in gpmi_predict.hip). Plain arithmetic, no HIP here, so
 // that the list is replayed on the host (tests/host/predict_plan_check.cpp).
 //
@@ -123,7 +123,7 @@ GPMI_PLAN_HD inline void predict_tile(int q, int ni, int nct, int* pi, int* pj) 
 }
 
 // ---------------------------------------------------------------------------
-// Joint covariance of the test points (gpmi_api.hip: gpmi_op_predict_cov; kernels
+// Joint covariance of the test points (gpmi_dense_predict.hip: gpmi_op_predict_cov; kernels
 // pred_cov_partial_kernel / pred_cov_reduce_kernel in gpmi_predict.hip):
 //   C0 = K** - V V^T,  V = L^-1 K*^T kept for ALL test points.
 // The working block is then the whole T [nsp][n_pad], nsp = n* rounded up to a tile;
