@@ -326,6 +326,50 @@ int forward_substitute(gpmi_op* op, const BatchPtrs& P) {
   return 0;
 }
 
+int traceinv_build_w(gpmi_op* op) {
+  DenseTraceInv& ti = op->tinv;
+  if (ti.gen != op->factor_gen) {
+    ti.gen = op->factor_gen;
+    ti.have = 0;
+  }
+  if (ti.have & 1) return 0;
+  const int nt = op->nt;
+  const int64_t np = op->n_pad;
+  const int ntri = nt * (nt + 1) / 2;
+  HIP_TRY(ti.W.reserve((size_t)np * np));
+  HIP_TRY(ti.tpart.reserve((size_t)(ntri + nt * nt)));
+  hipStream_t s = op->stream;
+  double* p1 = ti.tpart + ntri;   // [nt][nt]: ||Y_kj||^2 at [k * nt + j]
+  for (int kb = 0; kb < nt; kb += op->outer) {
+    const int ke = std::min(nt, kb + op->outer);
+    for (int k = kb; k < ke; ++k) {
+      if (k > kb) {
+        hipLaunchKernelGGL(trinv_update_kernel, dim3(k), dim3(256), 0, s, op->fac.A, np, ti.W,
+                           np, k, k, kb, k);
+        LAUNCH_CHECK("trinv_update_kernel");
+      }
+      hipLaunchKernelGGL(trinv_diag_kernel, dim3(k + 1), dim3(256), 0, s, op->fac.Linv, ti.W,
+                         np, k, p1 + (int64_t)k * nt);
+      LAUNCH_CHECK("trinv_diag_kernel");
+    }
+    if (ke < nt) {
+      hipLaunchKernelGGL(trinv_update_kernel, dim3((nt - ke) * ke), dim3(256), 0, s, op->fac.A,
+                         np, ti.W, np, ke, ke, kb, ke);
+      LAUNCH_CHECK("trinv_update_kernel");
+    }
+  }
+  std::vector<double> h((size_t)nt * nt);
+  HIP_TRY(hipMemcpyAsync(h.data(), p1, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  double acc = 0.0;
+  for (int k = 0; k < nt; ++k)
+    for (int j = 0; j <= k; ++j) acc += h[(size_t)k * nt + j];
+  // the identity pad contributes n_pad - n
+  ti.value[0] = acc - (double)(np - op->n);
+  ti.have |= 1;
+  return 0;
+}
+
 }  // namespace gpmi
 
 extern "C" {
@@ -423,72 +467,33 @@ int gpmi_op_traceinv(gpmi_op* op, double eta, int exponent, double* value) {
   bool fresh;
   int rc = factor_ready(op, eta, op->rhs_src, &fresh);
   if (rc) return rc;
+  // W = L^-T from the cached factor in slot 0 (needed by both exponents)
+  if ((rc = traceinv_build_w(op))) return rc;
   DenseTraceInv& ti = op->tinv;
-  if (ti.gen != op->factor_gen) {
-    ti.gen = op->factor_gen;
-    ti.have = 0;
-  }
-  const int bit = 1 << (exponent - 1);
-  if (!(ti.have & bit)) {
+  if (exponent == 2 && !(ti.have & 2)) {
     const int nt = op->nt;
     const int64_t np = op->n_pad;
-    const int ntri = nt * (nt + 1) / 2;
-    HIP_TRY(ti.W.reserve((size_t)np * np));
-    HIP_TRY(ti.tpart.reserve((size_t)(ntri + nt * nt)));
     HIP_TRY(ti.Td.reserve((size_t)nt * TS * TS));
     hipStream_t s = op->stream;
-    double* p1 = ti.tpart + ntri;   // [nt][nt]: ||Y_kj||^2 at [k * nt + j]
-    if (!(ti.have & 1)) {
-      // W = L^-T from the cached factor in slot 0 (needed by both exponents)
-      for (int kb = 0; kb < nt; kb += op->outer) {
-        const int ke = std::min(nt, kb + op->outer);
-        for (int k = kb; k < ke; ++k) {
-          if (k > kb) {
-            hipLaunchKernelGGL(trinv_update_kernel, dim3(k), dim3(256), 0, s, op->fac.A, np, ti.W,
-                               np, k, k, kb, k);
-            LAUNCH_CHECK("trinv_update_kernel");
-          }
-          hipLaunchKernelGGL(trinv_diag_kernel, dim3(k + 1), dim3(256), 0, s, op->fac.Linv, ti.W,
-                             np, k, p1 + (int64_t)k * nt);
-          LAUNCH_CHECK("trinv_diag_kernel");
-        }
-        if (ke < nt) {
-          hipLaunchKernelGGL(trinv_update_kernel, dim3((nt - ke) * ke), dim3(256), 0, s, op->fac.A,
-                             np, ti.W, np, ke, ke, kb, ke);
-          LAUNCH_CHECK("trinv_update_kernel");
-        }
-      }
-      std::vector<double> h((size_t)nt * nt);
-      HIP_TRY(hipMemcpyAsync(h.data(), p1, sizeof(double) * h.size(), hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      double acc = 0.0;
-      for (int k = 0; k < nt; ++k)
-        for (int j = 0; j <= k; ++j) acc += h[(size_t)k * nt + j];
-      // the identity pad contributes n_pad - n
-      ti.value[0] = acc - (double)(np - op->n);
-      ti.have |= 1;
+    // T = W W^T over k-panels of 4 tiles; panel [p0, p0 + kd) updates tile rows I < imax
+    for (int p0 = 0; p0 < (int)np; p0 += 4 * TS) {
+      const int kd = std::min<int>(4 * TS, (int)np - p0);
+      const int imax = (p0 + kd) / TS;
+      hipLaunchKernelGGL(gram_panel_kernel, dim3(imax * (imax + 1) / 2), dim3(256), 0, s,
+                         ti.W, np, ti.Td, p0, kd, imax);
+      LAUNCH_CHECK("gram_panel_kernel");
     }
-    if (exponent == 2) {
-      // T = W W^T over k-panels of 4 tiles; panel [p0, p0 + kd) updates tile rows I < imax
-      for (int p0 = 0; p0 < (int)np; p0 += 4 * TS) {
-        const int kd = std::min<int>(4 * TS, (int)np - p0);
-        const int imax = (p0 + kd) / TS;
-        hipLaunchKernelGGL(gram_panel_kernel, dim3(imax * (imax + 1) / 2), dim3(256), 0, s,
-                           ti.W, np, ti.Td, p0, kd, imax);
-        LAUNCH_CHECK("gram_panel_kernel");
-      }
-      hipLaunchKernelGGL(gram_sumsq_kernel, dim3(nt), dim3(256), 0, s, ti.W, np, ti.Td,
-                         ti.tpart);
-      LAUNCH_CHECK("gram_sumsq_kernel");
-      std::vector<double> h((size_t)nt);
-      HIP_TRY(hipMemcpyAsync(h.data(), ti.tpart, sizeof(double) * h.size(),
-                             hipMemcpyDeviceToHost, s));
-      HIP_TRY(hipStreamSynchronize(s));
-      double acc = 0.0;
-      for (int q = 0; q < nt; ++q) acc += h[q];
-      ti.value[1] = acc - (double)(np - op->n);
-      ti.have |= 2;
-    }
+    hipLaunchKernelGGL(gram_sumsq_kernel, dim3(nt), dim3(256), 0, s, ti.W, np, ti.Td,
+                       ti.tpart);
+    LAUNCH_CHECK("gram_sumsq_kernel");
+    std::vector<double> h((size_t)nt);
+    HIP_TRY(hipMemcpyAsync(h.data(), ti.tpart, sizeof(double) * h.size(),
+                           hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    double acc = 0.0;
+    for (int q = 0; q < nt; ++q) acc += h[q];
+    ti.value[1] = acc - (double)(np - op->n);
+    ti.have |= 2;
   }
   *value = ti.value[exponent - 1];
   return 0;

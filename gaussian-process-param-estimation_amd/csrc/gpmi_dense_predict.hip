@@ -14,14 +14,14 @@
 
 using namespace gpmi;
 
-namespace {
-
 // Y = L^-1 rhs_src for the cached factor into PY, and G = Y^T Y into Pgram[0..256):
 // from slot 0 of R when it still holds Y, else by forward substitution of rhs_src
 // again (a solve since the factorization has overwritten R).
-int predict_refresh_y(gpmi_op* op) {
+int gpmi::predict_refresh_y(gpmi_op* op) {
   DensePredict& p = op->pred;
   if (p.py_gen == op->factor_gen && p.py_rhs == op->rhs_gen) return 0;
+  HIP_TRY(p.PY.reserve((size_t)op->n_pad * RLD));
+  HIP_TRY(p.Pgram.reserve((size_t)(op->nt + 1) * 256));
   hipStream_t s = op->stream;
   BatchPtrs P = op->ptrs();
   if (p.ry_gen != op->factor_gen || p.ry_rhs != op->rhs_gen) {
@@ -41,6 +41,8 @@ int predict_refresh_y(gpmi_op* op) {
   p.py_rhs = op->rhs_gen;
   return 0;
 }
+
+namespace {
 
 // One call: its arguments, the shapes predict_check derives from them, and what the
 // steps hand on.
@@ -122,14 +124,12 @@ int predict_check(gpmi_op* op, PredictCall* c) {
 }
 
 // Workspace: grown to the widest chunk a call has needed, at most NS columns; PT holds
-// one chunk, or, for the covariance, every test column.
+// one chunk, or, for the covariance, every test column. (PY and Pgram: predict_refresh_y.)
 int predict_reserve(gpmi_op* op, const PredictCall& c) {
   DensePredict& p = op->pred;
   const int64_t np = op->n_pad;
   const PredictSizes sz = predict_sizes(np, op->nt, c.wide);
   const PredictCovSizes cz = predict_cov_sizes(np, c.cnct, c.csplit);
-  HIP_TRY(p.PY.reserve((size_t)np * RLD));
-  HIP_TRY(p.Pgram.reserve((size_t)(op->nt + 1) * 256));
   HIP_TRY(p.PT.reserve(c.cov ? cz.T : sz.T));
   HIP_TRY(p.Ppart.reserve(sz.part));
   HIP_TRY(p.Pout.reserve(sz.out));

@@ -114,6 +114,19 @@ __global__ void pred_cov_partial_kernel(const double* T, int64_t ldt, int nct, i
 __global__ void pred_cov_reduce_kernel(const double* part, int S, int nct, double* C,
                                        int64_t ldc);
 
+// Leave-one-out terms (gpmi_loo.hip): per row 16 entries of W Y, then the row's sum of
+// squares of W. One workgroup per LOO_ROWS rows and chunk of LOO_CHUNK columns (three
+// tiles: chunk starts 3 KB apart, not a power of two), Y staged in LDS in sub-blocks of
+// LOO_STAGE columns (32 KB).
+constexpr int LOO_LD = 17;
+constexpr int LOO_CHUNK = 384;
+constexpr int LOO_STAGE = 256;
+constexpr int LOO_ROWS = 64;
+__global__ void loo_pass_kernel(const double* W, int64_t ldw, const double* Y, int64_t n_pad,
+                                int cw, double* part);
+__global__ void loo_reduce_kernel(const double* part, int64_t n_pad, int cw, int nchunk,
+                                  double* out);
+
 // Multi-shift CG Gram state (gpmi_sparse.hip, gpmi_sparse_api.hip); device pointers.
 #ifndef GPMI_LZ_JC
 #define GPMI_LZ_JC 16

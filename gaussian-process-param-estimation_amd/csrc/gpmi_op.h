@@ -8,6 +8,7 @@
 //   gpmi_dense_factor.hip   the Cholesky schedule, its timing, and the calls that consume
 //                           a factor (DenseFactor, DenseTiming, DenseTraceInv)
 //   gpmi_dense_predict.hip  the prediction terms and the joint covariance (DensePredict)
+//   gpmi_dense_loo.hip      the leave-one-out terms (DenseLoo)
 // Every device buffer is a DevBuf, every stream and event an owner (gpmi_host.h):
 // destruction is member order, streams after the buffers their work may touch.
 #pragma once
@@ -79,6 +80,7 @@ struct DenseTiming {
   size_t colpanel_used = 0;
   EventPool pred;          // begin, end of a prediction call; (begin, end) per trailing product
   EventPool cov;           // begin, end of the covariance's partial-product launch
+  EventPool loo;           // begin, end of the leave-one-out pass over W
   std::vector<std::pair<int, double>> syrk_log;  // (event index, flops)
   std::vector<std::array<int, 3>> syrk_shape;    // (w, t, kdim) per logged launch
   double last_syrk_ms = 0.0, last_syrk_flops = 0.0, last_total_ms = 0.0;
@@ -116,6 +118,13 @@ struct DensePredict {
   int last_cov_split = 0;  // depth pieces of the last covariance call
 };
 
+// gpmi_op_loo_terms: workspace grown to the largest call so far.
+struct DenseLoo {
+  DevBuf<double> part;     // [nchunk][n_pad][17] per-chunk partials
+  DevBuf<double> out;      // [n_pad][17] (W Y)_i, then d_i
+  double last_ms = 0.0, last_bytes = 0.0;
+};
+
 }  // namespace gpmi
 
 struct gpmi_op {
@@ -142,6 +151,7 @@ struct gpmi_op {
   gpmi::DenseTiming tim;
   gpmi::DenseTraceInv tinv;
   gpmi::DensePredict pred;
+  gpmi::DenseLoo loo;
 
   gpmi::BatchPtrs ptrs() const { return fac.ptrs(n_pad, nt); }
 };
@@ -158,6 +168,13 @@ int upload_rhs(gpmi_op* op, double* dst, const double* rhs, int64_t ld, int nrhs
 int factor_ready(gpmi_op* op, double eta, const double* rhs_dev, bool* fresh);
 // R slot 0 <- L^-1 R slot 0 with the factor in slot 0.
 int forward_substitute(gpmi_op* op, const BatchPtrs& P);
+// W = L^-T of the cached factor in slot 0 into tinv.W, with tr((K + eta I)^-1) from the
+// same launches; nothing when tinv already holds them for this factorization.
+int traceinv_build_w(gpmi_op* op);
+
+// gpmi_dense_predict.hip
+// Y = L^-1 rhs_src for the cached factor into pred.PY, and G = Y^T Y into pred.Pgram[0..256).
+int predict_refresh_y(gpmi_op* op);
 
 }  // namespace gpmi
 

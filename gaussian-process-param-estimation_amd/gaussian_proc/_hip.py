@@ -68,6 +68,9 @@ SIGNATURES = {
                                            c_double_p, c_double_p, c_double_p, c_i64]),
     'gpmi_op_predict_cov_ms': (ctypes.c_int, [c_op_p, c_double_p, c_double_p]),
     'gpmi_op_predict_cov_split': (ctypes.c_int, [c_op_p, c_int_p]),
+    'gpmi_op_loo_terms': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p, c_double_p, c_i64,
+                                         c_double_p]),
+    'gpmi_op_loo_ms': (ctypes.c_int, [c_op_p, c_double_p, c_double_p]),
     'gpmi_last_assembly_ms': (ctypes.c_int, [c_double_p]),
     'gpmi_matern_values': (ctypes.c_int, [ctypes.c_int, c_double_p, c_i64, ctypes.c_double,
                                           c_double_p]),
@@ -446,6 +449,27 @@ class Operator(object):
         check(self.lib.gpmi_op_predict_ms(self.h, ctypes.byref(a), ctypes.byref(b),
                                           ctypes.byref(c)), 'gpmi_op_predict_ms')
         return dict(total_ms=a.value, trailing_ms=b.value, trailing_flops=c.value)
+
+    def loo_terms(self, eta):
+        """-> (dinv[n], sol[n, nrhs], gram[nrhs, nrhs]) for the resident RHS R and the
+        factor K + eta I = L L^T: dinv = diag((K + eta I)^-1), sol = (K + eta I)^-1 R,
+        gram = R^T (K + eta I)^-1 R, bit for bit predict_terms' (gpmi_op_loo_terms): one
+        pass over W = L^-T, the block traceinv builds and caches."""
+        m = self.nrhs
+        d = numpy.empty(self.n)
+        sol = numpy.empty((self.n, m))
+        g = numpy.empty((m, m))
+        check(self.lib.gpmi_op_loo_terms(self.h, float(eta), dptr(d), dptr(sol), m, dptr(g)),
+              'gpmi_op_loo_terms')
+        return d, sol, g
+
+    def loo_ms(self):
+        """-> dict(pass_ms, pass_bytes): the pass over W of the last loo_terms with
+        set_timing(True) (HIP events; 0 without) and the bytes of W it read."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        check(self.lib.gpmi_op_loo_ms(self.h, ctypes.byref(a), ctypes.byref(b)),
+              'gpmi_op_loo_ms')
+        return dict(pass_ms=a.value, pass_bytes=b.value)
 
 
 class Band(object):

@@ -96,6 +96,63 @@ def _predict_from_terms(c, q, G, Phi_star, sigma, sigma0, noise=False):
     return mean, var
 
 
+def _loo_from_terms(dinv, sol, G, z, sigma, sigma0, noise=True):
+    """Leave-one-out predictions of the n training values (universal kriging, beta
+    re-estimated without point i, sigma and sigma0 kept) from the terms of
+    MixedCorrelation.loo_terms. With S = K + eta I, eta = (sigma0 / sigma)^2 and
+    R = [X z]:
+      dinv[i] = (S^-1)_ii              (n)
+      sol     = S^-1 R                 (n x (m + 1))
+      G       = R^T S^-1 R             ((m + 1) x (m + 1))
+    Then, with B = G_XX, u_i the first m entries of row i of sol and
+    P = S^-1 - S^-1 X B^-1 X^T S^-1 (Dubrule 1983),
+      P_ii   = dinv_i - u_i^T B^-1 u_i
+      (Pz)_i = sol_iz - u_i^T B^-1 G_Xz
+      mean_i = z_i - (Pz)_i / P_ii
+      var_i  = sigma^2 / P_ii          (the noisy observation; ``noise=False``
+                                        subtracts sigma0^2: the latent function)
+    m = 0 (no basis) leaves P = S^-1. -> (mean, var)."""
+    dinv = numpy.asarray(dinv, dtype=float)
+    sol = numpy.asarray(sol, dtype=float)
+    G = numpy.asarray(G, dtype=float)
+    z = numpy.asarray(z, dtype=float)
+    m = G.shape[0] - 1
+    n = dinv.shape[0]
+    if m < 0 or G.shape != (m + 1, m + 1) or dinv.ndim != 1 or sol.shape != (n, m + 1) or \
+            z.shape != (n,):
+        raise ValueError('dinv and z must be n, sol n x (m + 1) and G (m + 1) x (m + 1)')
+    if not sigma > 0.0:
+        raise ValueError('sigma must be positive')
+    if m == 0:
+        pii, pz = dinv, sol[:, 0]
+    else:
+        B = G[:m, :m]
+        u = sol[:, :m]
+        Biu = numpy.linalg.solve(B, u.T).T
+        pii = dinv - numpy.sum(u * Biu, axis=1)
+        pz = sol[:, m] - Biu @ G[:m, m]
+    mean = z - pz / pii
+    var = sigma ** 2 / pii
+    if not noise:
+        var = var - sigma0 ** 2
+    return mean, var
+
+
+def _cross_validation_scores(z, mean, var):
+    """The summary scores of GaussianProcess.cross_validate from the leave-one-out
+    mean and (noisy) variance. -> dict."""
+    z = numpy.asarray(z, dtype=float)
+    residual = z - mean
+    return {
+        'residual': residual,
+        'standardized': residual / numpy.sqrt(var),
+        'rmse': float(numpy.sqrt(numpy.mean(residual ** 2))),
+        'mean_squared_standardized': float(numpy.mean(residual ** 2 / var)),
+        'log_pseudo_likelihood': float(numpy.sum(-0.5 * numpy.log(2.0 * numpy.pi * var) -
+                                                 residual ** 2 / (2.0 * var))),
+    }
+
+
 def _predict_cov_from_terms(c, G, C0, Phi_star, sigma, sigma0, noise=False):
     """Joint posterior covariance of n* new points (universal kriging) from the
     terms of MixedCorrelation.predict_cov_terms: c and G as in _predict_from_terms

@@ -726,6 +726,23 @@ class MixedCorrelation(object):
                                    scale=correlation_scale, nu=nu, cross=cross,
                                    cross_star=cross_star)
 
+    def loo_terms(self, eta, X, z):
+        """The device terms of leave-one-out cross-validation (the reference has no
+        counterpart). With S = K + eta I and R = [X z]:
+          dinv[n] = diag(S^-1),   sol[n, m + 1] = S^-1 R,   G[m + 1, m + 1] = R^T S^-1 R,
+        from the dense Cholesky of S (cached per eta), its triangular inverse
+        W = L^-T (the one traceinv builds, cached with the factor) and one fused pass
+        over W (csrc/gpmi_loo.hip); _loo_from_terms turns them into the n
+        leave-one-out predictions. A sparse K raises NotImplementedError; K + eta I
+        not positive definite raises numpy.linalg.LinAlgError. Returns (dinv, sol, G)."""
+        if self.sparse:
+            raise NotImplementedError('leave-one-out on a sparse K is not implemented')
+        X = numpy.asarray(X, dtype=float)
+        if X.ndim != 2 or X.shape[0] != self.n:
+            raise ValueError('X must be %d x m' % self.n)
+        self.set_rhs(X, z)
+        return self.op.loo_terms(eta)
+
     def _predict_args(self, X, test_points, cross, points, correlation_scale, nu, who):
         """The checks and kernel-parameter defaults predict_terms and
         predict_cov_terms share -> (test_points, points, correlation_scale, nu)."""

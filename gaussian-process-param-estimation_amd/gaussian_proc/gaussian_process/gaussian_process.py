@@ -1,11 +1,13 @@
 """Gaussian process user class (drop-in for
 gaussian_proc/gaussian_process/gaussian_process.py:21-71), with the prediction
-the reference leaves as a commented-out stub."""
+the reference leaves as a commented-out stub, and leave-one-out cross-validation
+of the fitted model."""
 
 import numpy
 
 from .._likelihood import Likelihood
-from .._likelihood._profile_likelihood import _predict_from_terms, _predict_cov_from_terms
+from .._likelihood._profile_likelihood import _predict_from_terms, _predict_cov_from_terms, \
+    _loo_from_terms, _cross_validation_scores
 
 __all__ = ['GaussianProcess']
 
@@ -87,3 +89,53 @@ class GaussianProcess(object):
                                                         **kernel_params)
         mean, var = _predict_from_terms(c, q, G, X_star, sigma, sigma0, noise=noise)
         return (mean, var) if return_var else mean
+
+    def _loo_args(self, z, hyperparam, who):
+        """z and (sigma, sigma0), defaulting to the last train, checked. -> (X, z, sigma,
+        sigma0)."""
+        if z is None:
+            z = self.z
+        if hyperparam is None and self.results is not None:
+            hyperparam = (self.results['sigma'], self.results['sigma0'])
+        if z is None or hyperparam is None:
+            raise ValueError('%s needs z and hyperparam=(sigma, sigma0), or an earlier '
+                             'train(z)' % who)
+        sigma, sigma0 = float(hyperparam[0]), float(hyperparam[1])
+        if not sigma > 0.0:
+            raise ValueError('sigma must be positive')
+        X = numpy.asarray(self.X, dtype=float)
+        n, m = X.shape
+        if n <= m:
+            raise ValueError('leave-one-out needs more points than basis functions '
+                             '(n = %d, m = %d)' % (n, m))
+        z = numpy.asarray(z, dtype=float)
+        if z.shape != (n,):
+            raise ValueError('z must have %d entries' % n)
+        return X, z, sigma, sigma0
+
+    def leave_one_out(self, z=None, hyperparam=None, noise=True, return_var=True):
+        """Leave-one-out cross-validation in closed form: for every training point i
+        the prediction of z_i, and its variance, from the other n - 1 points, with
+        ``hyperparam = (sigma, sigma0)`` kept and beta re-estimated without point i
+        (what ``predict`` on the reduced data set would return at point i). With
+        S = K + (sigma0 / sigma)^2 I and P = S^-1 - S^-1 X (X^T S^-1 X)^-1 X^T S^-1,
+          mean_i = z_i - (P z)_i / P_ii,   var_i = sigma^2 / P_ii,
+        the variance of the noisy observation z_i (``noise=False`` subtracts sigma0^2:
+        the latent function). One factorization and one pass over its triangular
+        inverse on the device (MixedCorrelation.loo_terms), not n refits. ``z`` and
+        ``hyperparam`` default to those of the last ``train``.
+        -> mean, or (mean, var) with ``return_var``."""
+        X, z, sigma, sigma0 = self._loo_args(z, hyperparam, 'leave_one_out')
+        dinv, sol, G = self.likelihood.K_mixed.loo_terms((sigma0 / sigma) ** 2, X, z)
+        mean, var = _loo_from_terms(dinv, sol, G, z, sigma, sigma0, noise=noise)
+        return (mean, var) if return_var else mean
+
+    def cross_validate(self, z=None, hyperparam=None):
+        """Leave-one-out scores of the fitted model -> dict with 'residual'
+        (z - mean), 'standardized' (residual / sqrt(var), the noisy variance), 'rmse',
+        'mean_squared_standardized' (about 1 for a well-calibrated model) and
+        'log_pseudo_likelihood' = sum_i -log(2 pi var_i) / 2 - residual_i^2 / (2 var_i).
+        Arguments as ``leave_one_out``."""
+        X, z, sigma, sigma0 = self._loo_args(z, hyperparam, 'cross_validate')
+        mean, var = self.leave_one_out(z=z, hyperparam=(sigma, sigma0), noise=True)
+        return _cross_validation_scores(z, mean, var)

@@ -195,6 +195,28 @@ int gpmi_op_predict_cov(gpmi_op* op, double eta, const double* points, int d,
 int gpmi_op_predict_cov_ms(gpmi_op* op, double* product_ms, double* product_flops);
 int gpmi_op_predict_cov_split(gpmi_op* op, int* split);
 
+/* ---------------------------------------------------------- leave-one-out --
+ * Like the prediction, an extension beyond the reference; serves
+ * gaussian_proc.GaussianProcess.leave_one_out / cross_validate of this build. */
+
+/* Leave-one-out terms from the cached factor of K + eta I (factorized if absent)
+ * and the resident RHS block R: dinv_out[n] = diag((K+eta I)^-1),
+ * sol_out[n][ldsol] = (K+eta I)^-1 R (nrhs columns), gram_out[nrhs][nrhs] = R^T (K+eta I)^-1 R.
+ * With W = L^-T (the block gpmi_op_traceinv builds and caches per factorization;
+ * either call reuses the other's) and Y = L^-1 R, one pass over the upper block
+ * triangle of W gives d_i = sum_k W_ik^2 and row i of W Y together. The column
+ * range is cut into chunks of 384 columns whose partial sums are added in
+ * ascending order (no atomics: the same input gives the same bits); the
+ * environment variable GPMI_LOO_CHUNK (columns, a multiple of 128, read per
+ * call) overrides the width. gram_out is bit for bit that of gpmi_op_predict_terms.
+ * Any output may be NULL. > 0: first non-positive pivot; < 0: null handle, no resident RHS,
+ * ldsol < nrhs. */
+int gpmi_op_loo_terms(gpmi_op* op, double eta, double* dinv_out, double* sol_out,
+                      int64_t ldsol, double* gram_out);
+/* HIP-event ms of the last call's fused pass and the bytes of W it read
+ * (when gpmi_op_set_timing is on). */
+int gpmi_op_loo_ms(gpmi_op* op, double* pass_ms, double* pass_bytes);
+
 /* ------------------------------------------------------------------ sparse --
  * Tapered (compact-support) Matérn correlation in CSR on the device, and the
  * Krylov primitives of the sparse likelihood path. Replaces
