@@ -1,5 +1,6 @@
 // The dense operator's prediction terms and joint covariance (include/gpmi.h:
-// gpmi_op_predict_terms, gpmi_op_predict_cov; gpmi_op.h: DensePredict) on the cached
+// gpmi_op_predict_terms, gpmi_op_predict_cov, gpmi_op_predict_cov_resident; gpmi_op.h:
+// DensePredict) on the cached
 // factor: chunking, launch list and workspace sizes are gpmi_predict_plan.h, the kernels
 // gpmi_predict.hip.
 
@@ -56,6 +57,7 @@ struct PredictCall {
   const double* kss;           // K** that goes with an uploaded kstar
   int64_t ldkss, ldcov;
   double* cov_out;
+  bool resident;               // gpmi_op_predict_cov_resident: C0 stays on the device only
   MaternParams MP;
   int NS;                      // chunk width in columns
   int wide;                    // the widest chunk of this call, in columns
@@ -82,8 +84,8 @@ int predict_check(gpmi_op* op, PredictCall* c) {
     return set_errorf(-1014, "ldks %lld below n = %lld", (long long)c->ldks, (long long)op->n);
   }
   if (c->cov) {
-    if (!c->cov_out) return set_error(-1004, "null argument");
-    if (c->ldcov < nstar)
+    if (!c->cov_out && !c->resident) return set_error(-1004, "null argument");
+    if (c->cov_out && c->ldcov < nstar)
       return set_errorf(-1016, "ldcov %lld below nstar = %lld", (long long)c->ldcov,
                         (long long)nstar);
     if (c->kstar && !c->kss)
@@ -134,6 +136,7 @@ int predict_reserve(gpmi_op* op, const PredictCall& c) {
   HIP_TRY(p.Ppart.reserve(sz.part));
   HIP_TRY(p.Pout.reserve(sz.out));
   if (c.cov) {
+    p.cov_nstar = 0;   // (Pcov is about to be overwritten, or moved)
     HIP_TRY(p.Pcov.reserve(cz.cov));
     HIP_TRY(p.Pcpart.reserve(cz.part));
     if (op->tim.on) HIP_TRY(op->tim.cov.reserve(2, timing_event_flags()));
@@ -224,9 +227,11 @@ int predict_cov_tail(gpmi_op* op, const PredictCall& c) {
   hipLaunchKernelGGL(pred_cov_reduce_kernel, dim3(ntiles, TS / 16), dim3(256), 0, s, p.Pcpart,
                      c.csplit, c.cnct, p.Pcov, ldc);
   LAUNCH_CHECK("pred_cov_reduce_kernel");
-  HIP_TRY(hipMemcpy2DAsync(c.cov_out, sizeof(double) * c.ldcov, p.Pcov, sizeof(double) * ldc,
-                           sizeof(double) * nstar, nstar, hipMemcpyDeviceToHost, s));
+  if (c.cov_out)
+    HIP_TRY(hipMemcpy2DAsync(c.cov_out, sizeof(double) * c.ldcov, p.Pcov, sizeof(double) * ldc,
+                             sizeof(double) * nstar, nstar, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
+  p.cov_nstar = nstar;   // Pcov holds C0 of this call (gpmi_op_load_predict_cov reads it)
   p.last_cov_ms = p.last_cov_flops = 0.0;
   p.last_cov_split = c.csplit;
   if (op->tim.on) {
@@ -259,9 +264,10 @@ int predict_read_timing(gpmi_op* op, const PredictCall& c) {
   return 0;
 }
 
-// gpmi_op_predict_terms and gpmi_op_predict_cov. Without `cov` the working block holds
-// one chunk at a time; with it every chunk keeps its rows of the whole block, and
-// C0 = K** - V V^T follows the chunks.
+// gpmi_op_predict_terms, gpmi_op_predict_cov and gpmi_op_predict_cov_resident. Without
+// `cov` the working block holds one chunk at a time; with it every chunk keeps its rows of
+// the whole block, and C0 = K** - V V^T follows the chunks (`resident`: the same launches
+// without the download of C0).
 int predict_run(gpmi_op* op, PredictCall* c) {
   if (!op) return set_error(-1006, "null handle");
   int rc = predict_check(op, c);
@@ -323,6 +329,17 @@ int gpmi_op_predict_cov(gpmi_op* op, double eta, const double* points, int d,
   PredictCall c = {eta,   nu,   d,     points, scale,    test_points, kstar,
                    nstar, ldks, c_out, q_out,  gram_out, true,        kss,
                    ldkss, ldcov, cov_out};
+  return predict_run(op, &c);
+}
+
+int gpmi_op_predict_cov_resident(gpmi_op* op, double eta, const double* points, int d,
+                                 const double* scale, double nu, const double* test_points,
+                                 int64_t nstar, const double* kstar, int64_t ldks,
+                                 const double* kss, int64_t ldkss, double* c_out,
+                                 double* q_out, double* gram_out) {
+  PredictCall c = {eta,   nu,   d,     points, scale,    test_points, kstar,
+                   nstar, ldks, c_out, q_out,  gram_out, true,        kss,
+                   ldkss, 0,    nullptr, true};
   return predict_run(op, &c);
 }
 

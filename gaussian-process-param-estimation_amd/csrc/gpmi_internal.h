@@ -127,6 +127,17 @@ __global__ void loo_pass_kernel(const double* W, int64_t ldw, const double* Y, i
 __global__ void loo_reduce_kernel(const double* part, int64_t n_pad, int cw, int nchunk,
                                   double* out);
 
+// Draws from the cached factor and the covariance hand-over (gpmi_sample.hip; work list in
+// gpmi_sample_plan.h).
+__global__ void sample_normal_kernel(double* Xi, int64_t ld, int64_t rows, int64_t cols,
+                                     unsigned long long seed, unsigned long long first);
+__global__ void sample_trmm_kernel(const double* L, int64_t lda, const double* Xi, int64_t ldx,
+                                   int jt, int D, int split, const uint32_t* order, double* Y,
+                                   int64_t ldy, double* part);
+__global__ void sample_reduce_kernel(const double* part, int jt, int D, double* Y, int64_t ldy);
+__global__ void cov_lowrank_kernel(const double* src, int64_t lds, double* dst, int64_t np,
+                                   int64_t n, const double* U, int m);
+
 // Multi-shift CG Gram state (gpmi_sparse.hip, gpmi_sparse_api.hip); device pointers.
 #ifndef GPMI_LZ_JC
 #define GPMI_LZ_JC 16

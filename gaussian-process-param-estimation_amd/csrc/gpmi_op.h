@@ -9,6 +9,8 @@
 //                           a factor (DenseFactor, DenseTiming, DenseTraceInv)
 //   gpmi_dense_predict.hip  the prediction terms and the joint covariance (DensePredict)
 //   gpmi_dense_loo.hip      the leave-one-out terms (DenseLoo)
+//   gpmi_dense_sample.hip   draws from the cached factor, and the hand-over of the joint
+//                           covariance to a second operator (DenseSample)
 // Every device buffer is a DevBuf, every stream and event an owner (gpmi_host.h):
 // destruction is member order, streams after the buffers their work may touch.
 #pragma once
@@ -81,6 +83,7 @@ struct DenseTiming {
   EventPool pred;          // begin, end of a prediction call; (begin, end) per trailing product
   EventPool cov;           // begin, end of the covariance's partial-product launch
   EventPool loo;           // begin, end of the leave-one-out pass over W
+  EventPool samp;          // per chunk of draws: begin, end of the normals and of the product
   std::vector<std::pair<int, double>> syrk_log;  // (event index, flops)
   std::vector<std::array<int, 3>> syrk_shape;    // (w, t, kdim) per logged launch
   double last_syrk_ms = 0.0, last_syrk_flops = 0.0, last_total_ms = 0.0;
@@ -110,6 +113,8 @@ struct DensePredict {
   DevBuf<double> Pcov;     // [nsp][nsp] K**, then C0 = K** - V V^T
   DevBuf<double> Pcpart;   // [tiles][S][128][128] depth pieces of the product
   int ncu = 0;             // compute units (read at the first covariance call)
+  int64_t cov_nstar = 0;   // Pcov holds C0 of this many points, leading dimension their
+                           // count rounded up to a tile (0: nothing resident)
   uint64_t ry_gen = ~0ull; // factor generation for which R slot 0 holds L^-1 rhs_src
   uint64_t ry_rhs = ~0ull; // ... and the rhs generation
   uint64_t py_gen = ~0ull, py_rhs = ~0ull;   // the same for PY / Pgram
@@ -123,6 +128,19 @@ struct DenseLoo {
   DevBuf<double> part;     // [nchunk][n_pad][17] per-chunk partials
   DevBuf<double> out;      // [n_pad][17] (W Y)_i, then d_i
   double last_ms = 0.0, last_bytes = 0.0;
+};
+
+// gpmi_op_sample / gpmi_op_load_predict_cov: workspace of one chunk of draws, grown to
+// the largest so far (sizes and work list: gpmi_sample_plan.h).
+struct DenseSample {
+  DevBuf<double> Xi;       // [chunk][n_pad] the normals, sample-major
+  DevBuf<double> Y;        // [chunk][n_pad] the draws
+  DevBuf<double> part;     // [pieces][draw tiles][128][128] depth pieces of the product
+  DevBuf<uint32_t> order;  // the pieces, deepest first, for (order_nt, order_depth)
+  int order_nt = -1, order_depth = -1;
+  DevBuf<double> U;        // [n][m] the low-rank factor of gpmi_op_load_predict_cov
+  Event ev_src;            // the source operator's work -> this operator's stream
+  double last_normal_ms = 0.0, last_trmm_ms = 0.0, last_trmm_flops = 0.0;
 };
 
 }  // namespace gpmi
@@ -152,6 +170,7 @@ struct gpmi_op {
   gpmi::DenseTraceInv tinv;
   gpmi::DensePredict pred;
   gpmi::DenseLoo loo;
+  gpmi::DenseSample samp;
 
   gpmi::BatchPtrs ptrs() const { return fac.ptrs(n_pad, nt); }
 };

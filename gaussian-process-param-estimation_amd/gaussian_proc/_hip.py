@@ -71,6 +71,17 @@ SIGNATURES = {
     'gpmi_op_loo_terms': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p, c_double_p, c_i64,
                                          c_double_p]),
     'gpmi_op_loo_ms': (ctypes.c_int, [c_op_p, c_double_p, c_double_p]),
+    'gpmi_op_predict_cov_resident': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p,
+                                                    ctypes.c_int, c_double_p, ctypes.c_double,
+                                                    c_double_p, c_i64, c_double_p, c_i64,
+                                                    c_double_p, c_i64, c_double_p, c_double_p,
+                                                    c_double_p]),
+    'gpmi_op_load_predict_cov': (ctypes.c_int, [c_op_p, c_op_p, c_double_p, c_i64,
+                                                ctypes.c_int]),
+    'gpmi_op_sample': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p, c_i64,
+                                      ctypes.c_ulonglong, ctypes.c_ulonglong, c_i64, c_double_p,
+                                      c_i64]),
+    'gpmi_op_sample_ms': (ctypes.c_int, [c_op_p, c_double_p, c_double_p, c_double_p]),
     'gpmi_last_assembly_ms': (ctypes.c_int, [c_double_p]),
     'gpmi_matern_values': (ctypes.c_int, [ctypes.c_int, c_double_p, c_i64, ctypes.c_double,
                                           c_double_p]),
@@ -383,15 +394,9 @@ class Operator(object):
                                              dptr(g)), 'gpmi_op_predict_terms')
         return c, q, g
 
-    def predict_cov(self, eta, test_points=None, points=None, scale=None, nu=None,
-                    cross=None, cross_star=None):
-        """-> (c, q, gram, C0): predict_terms' three, bit for bit, and
-        C0[nstar, nstar] = K** - K* (K + eta I)^-1 K*^T, exactly symmetric
-        (gpmi_op_predict_cov). K**, the correlations of the test points with each
-        other, is assembled on the device with k*, or, with the host matrix ``cross``
-        (nstar x n), taken from ``cross_star`` (nstar x nstar; its lower triangle is
-        read)."""
-        m = self.nrhs
+    def _predict_cov_args(self, who, test_points, points, scale, nu, cross, cross_star):
+        """The checks predict_cov and predict_cov_resident share -> (nstar, the C
+        arguments from points to ldkss)."""
         if cross is not None:
             cross = as_c(cross)
             if cross.ndim != 2 or cross.shape[1] != self.n or cross.shape[0] < 1:
@@ -403,32 +408,105 @@ class Operator(object):
             cross_star = as_c(cross_star)
             if cross_star.shape != (nstar, nstar):
                 raise ValueError('cross_star must be %d x %d' % (nstar, nstar))
-            args = (None, 0, None, 0.0, None, nstar, dptr(cross), self.n, dptr(cross_star),
-                    nstar)
-        else:
-            if test_points is None or points is None or scale is None or nu is None:
-                raise ValueError('predict_cov needs test_points, points, scale and nu, '
-                                 'or cross and cross_star')
-            points = as_c(points)
-            test_points = as_c(test_points)
-            scale = as_c(scale)
-            if points.ndim != 2 or points.shape[0] != self.n:
-                raise ValueError('points must be %d x d' % self.n)
-            d = points.shape[1]
-            if test_points.ndim != 2 or test_points.shape[1] != d or test_points.shape[0] < 1:
-                raise ValueError('test_points must be nstar x %d with nstar >= 1' % d)
-            if scale.shape != (d,):
-                raise ValueError('scale must have one entry per dimension (%d)' % d)
-            nstar = test_points.shape[0]
-            args = (dptr(points), d, dptr(scale), float(nu), dptr(test_points), nstar, None, 0,
-                    None, 0)
+            # (the arrays ride along: the pointers must outlive the call)
+            return nstar, (None, 0, None, 0.0, None, nstar, dptr(cross), self.n,
+                           dptr(cross_star), nstar), (cross, cross_star)
+        if test_points is None or points is None or scale is None or nu is None:
+            raise ValueError('%s needs test_points, points, scale and nu, '
+                             'or cross and cross_star' % who)
+        points = as_c(points)
+        test_points = as_c(test_points)
+        scale = as_c(scale)
+        if points.ndim != 2 or points.shape[0] != self.n:
+            raise ValueError('points must be %d x d' % self.n)
+        d = points.shape[1]
+        if test_points.ndim != 2 or test_points.shape[1] != d or test_points.shape[0] < 1:
+            raise ValueError('test_points must be nstar x %d with nstar >= 1' % d)
+        if scale.shape != (d,):
+            raise ValueError('scale must have one entry per dimension (%d)' % d)
+        nstar = test_points.shape[0]
+        return nstar, (dptr(points), d, dptr(scale), float(nu), dptr(test_points), nstar, None,
+                       0, None, 0), (points, test_points, scale)
+
+    def predict_cov(self, eta, test_points=None, points=None, scale=None, nu=None,
+                    cross=None, cross_star=None):
+        """-> (c, q, gram, C0): predict_terms' three, bit for bit, and
+        C0[nstar, nstar] = K** - K* (K + eta I)^-1 K*^T, exactly symmetric
+        (gpmi_op_predict_cov). K**, the correlations of the test points with each
+        other, is assembled on the device with k*, or, with the host matrix ``cross``
+        (nstar x n), taken from ``cross_star`` (nstar x nstar; its lower triangle is
+        read)."""
+        m = self.nrhs
+        nstar, args, keep = self._predict_cov_args('predict_cov', test_points, points, scale,
+                                                   nu, cross, cross_star)
         c = numpy.empty((nstar, m))
         q = numpy.empty(nstar)
         g = numpy.empty((m, m))
         cov = numpy.empty((nstar, nstar))
         check(self.lib.gpmi_op_predict_cov(self.h, float(eta), *args, dptr(c), dptr(q), dptr(g),
                                            dptr(cov), nstar), 'gpmi_op_predict_cov')
+        del keep
         return c, q, g, cov
+
+    def predict_cov_resident(self, eta, test_points=None, points=None, scale=None, nu=None,
+                             cross=None, cross_star=None):
+        """-> (c, q, gram), bit for bit predict_cov's: the same call without the
+        download of C0, which stays on the device for ``load_predict_cov`` of a second
+        operator (gpmi_op_predict_cov_resident)."""
+        m = self.nrhs
+        nstar, args, keep = self._predict_cov_args('predict_cov_resident', test_points, points,
+                                                   scale, nu, cross, cross_star)
+        c = numpy.empty((nstar, m))
+        q = numpy.empty(nstar)
+        g = numpy.empty((m, m))
+        check(self.lib.gpmi_op_predict_cov_resident(self.h, float(eta), *args, dptr(c), dptr(q),
+                                                    dptr(g)), 'gpmi_op_predict_cov_resident')
+        del keep
+        return c, q, g
+
+    def load_predict_cov(self, src, U=None):
+        """K <- C0 + U U^T on the device, C0 the covariance block the last
+        ``predict_cov`` / ``predict_cov_resident`` of the operator ``src`` left resident
+        (this operator's n is its nstar) and U (n x m, m <= 15; None: C0 alone)
+        (gpmi_op_load_predict_cov). Exactly symmetric; drops the cached factor."""
+        if U is None:
+            U = numpy.empty((self.n, 0))
+        U = as_c(U)
+        if U.ndim != 2 or U.shape[0] != self.n:
+            raise ValueError('U must be %d x m' % self.n)
+        m = U.shape[1]
+        check(self.lib.gpmi_op_load_predict_cov(self.h, src.h, dptr(U) if m else None, m, m),
+              'gpmi_op_load_predict_cov')
+        self.generation += 1
+
+    def sample(self, eta, size, seed=0, first=0, xi=None):
+        """-> draws (size, n) of N(0, K + eta I): row j = L xi_j with K + eta I = L L^T the
+        cached factor (gpmi_op_sample). xi_j is column j of ``xi`` (n x size) when given,
+        else generated on the device for the draw indices first .. first + size under
+        ``seed`` (gaussian_proc._normal.standard_normals states the values)."""
+        size = int(size)
+        if size < 1:
+            raise ValueError('size must be at least 1')
+        if int(seed) < 0 or int(first) < 0:
+            raise ValueError('seed and first must be non-negative')
+        if xi is not None:
+            xi = as_c(xi)
+            if xi.shape != (self.n, size):
+                raise ValueError('xi must be %d x %d' % (self.n, size))
+        out = numpy.empty((size, self.n))
+        check(self.lib.gpmi_op_sample(self.h, float(eta), None if xi is None else dptr(xi), size,
+                                      int(seed) & (2 ** 64 - 1), int(first) & (2 ** 64 - 1),
+                                      size, dptr(out), self.n), 'gpmi_op_sample')
+        return out
+
+    def sample_ms(self):
+        """-> dict(normal_ms, trmm_ms, trmm_flops): the normal generation and the
+        triangular product of the last sample with set_timing(True) (HIP events; 0
+        without), summed over its chunks."""
+        a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()
+        check(self.lib.gpmi_op_sample_ms(self.h, ctypes.byref(a), ctypes.byref(b),
+                                         ctypes.byref(c)), 'gpmi_op_sample_ms')
+        return dict(normal_ms=a.value, trmm_ms=b.value, trmm_flops=c.value)
 
     def predict_cov_ms(self):
         """-> dict(product_ms, product_flops, split): the partial-product launch of the

@@ -17,6 +17,7 @@ with the same algebra written in those blocks (_der_from_terms).
 """
 
 import numpy
+from scipy.linalg import solve_triangular
 from scipy.optimize import minimize
 from functools import partial
 
@@ -183,6 +184,28 @@ def _predict_cov_from_terms(c, G, C0, Phi_star, sigma, sigma0, noise=False):
     if noise:
         cov[numpy.diag_indices_from(cov)] += sigma0 ** 2
     return cov
+
+
+def _sample_lowrank_from_terms(c, G, Phi_star):
+    """The rank-m trend term of the joint posterior covariance as a factor: U (n* x m)
+    with U U^T = r B^-1 r^T, r = Phi_star - c_X and B = G_XX, the same r and block
+    _predict_cov_from_terms uses, so that C0 + U U^T is its covariance in units of
+    sigma^2 (noise off). With B = L_B L_B^T, U = r L_B^-T: one Cholesky of the m x m
+    block and one triangular solve. m = 0 gives an (n*, 0) U. B not positive definite
+    raises numpy.linalg.LinAlgError. -> U."""
+    c = numpy.asarray(c, dtype=float)
+    G = numpy.asarray(G, dtype=float)
+    m = G.shape[0] - 1
+    if m < 0 or G.shape != (m + 1, m + 1) or c.ndim != 2 or c.shape[1] != m + 1:
+        raise ValueError('c must be n* x (m + 1) and G (m + 1) x (m + 1)')
+    Phi = numpy.asarray(Phi_star, dtype=float).reshape(c.shape[0], -1)
+    if Phi.shape[1] != m:
+        raise ValueError('Phi_star must be n* x %d' % m)
+    if m == 0:
+        return numpy.empty((c.shape[0], 0))
+    r = Phi - c[:, :m]
+    LB = numpy.linalg.cholesky(G[:m, :m])
+    return numpy.ascontiguousarray(solve_triangular(LB, r.T, lower=True).T)
 
 
 class ProfileLikelihood(object):

@@ -743,6 +743,65 @@ class MixedCorrelation(object):
         self.set_rhs(X, z)
         return self.op.loo_terms(eta)
 
+    def sample(self, eta, size=1, seed=0, first=0, xi=None):
+        """Draws of N(0, K + eta I) for a dense K (the reference has no counterpart):
+        row j of the result is L xi_j with K + eta I = L L^T the dense Cholesky factor
+        (cached per eta) and the triangular product on fp64 MFMA
+        (csrc/gpmi_sample.hip). xi_j is column j of ``xi`` (n x size) when given, else
+        the device generator's draw of index ``first + j`` under ``seed``
+        (gaussian_proc._normal.standard_normals states its values), so that draws can
+        be taken in batches that continue each other. A sparse K raises
+        NotImplementedError; K + eta I not positive definite raises
+        numpy.linalg.LinAlgError. Returns draws (size, n)."""
+        if self.sparse:
+            raise NotImplementedError('sampling on a sparse K is not implemented')
+        return self.op.sample(eta, size, seed=seed, first=first, xi=xi)
+
+    def posterior_sample_terms(self, eta, X, z, size=1, test_points=None, cross=None,
+                               cross_star=None, X_star=None, extra_eta=0.0, seed=0, first=0,
+                               xi=None, points=None, correlation_scale=None, nu=None):
+        """Joint posterior draws at n* new points, in correlation units and about zero:
+        predict_cov_terms' c and G, and draws (size, n*) of N(0, C0 + U U^T + extra_eta I)
+        with C0 = K** - K* S^-1 K*^T and U U^T the trend term r (X^T S^-1 X)^-1 r^T of the
+        basis rows ``X_star`` (n* x m; _sample_lowrank_from_terms). C0 never leaves the
+        device: it stays resident after the covariance product, a second dense
+        operator of size n* (kept, re-created when n* changes) takes C0 + U U^T as its
+        own K on the device, factors it with the batched Cholesky and multiplies the
+        factor with the normals (``xi`` (n* x size), or the device generator under
+        ``seed`` from draw ``first``). Kernel parameters resolve as in predict_terms.
+        A covariance that is not numerically positive definite raises
+        numpy.linalg.LinAlgError. Returns (c, G, draws)."""
+        from .._likelihood._profile_likelihood import _sample_lowrank_from_terms
+        test_points, points, correlation_scale, nu = self._predict_args(
+            X, test_points, cross, points, correlation_scale, nu, 'posterior_sample_terms')
+        if cross is not None and cross_star is None:
+            raise ValueError('cross needs cross_star, the n* x n* correlations of the new '
+                             'points with each other')
+        if int(size) < 1:
+            raise ValueError('size must be at least 1')
+        self.set_rhs(X, z)
+        c, _, G = self.op.predict_cov_resident(eta, test_points=test_points, points=points,
+                                               scale=correlation_scale, nu=nu, cross=cross,
+                                               cross_star=cross_star)
+        nstar = c.shape[0]
+        if X_star is None:
+            X_star = numpy.empty((nstar, 0))
+        U = _sample_lowrank_from_terms(c, G, X_star)
+        child = getattr(self, '_sample_child', None)
+        if child is None or child.n != nstar:
+            if child is not None:
+                child.close()
+            child = self._sample_child = _hip.Operator(nstar, device=self.op.device)
+        child.load_predict_cov(self.op, U)
+        try:
+            draws = child.sample(extra_eta, size, seed=seed, first=first, xi=xi)
+        except numpy.linalg.LinAlgError as e:
+            raise numpy.linalg.LinAlgError(
+                'the joint covariance of the new points plus %g I is not numerically positive '
+                'definite (%s): a jitter on its diagonal (GaussianProcess.sample: jitter=) or '
+                'the noise term (noise=True) are the remedies' % (extra_eta, e))
+        return c, G, draws
+
     def _predict_args(self, X, test_points, cross, points, correlation_scale, nu, who):
         """The checks and kernel-parameter defaults predict_terms and
         predict_cov_terms share -> (test_points, points, correlation_scale, nu)."""

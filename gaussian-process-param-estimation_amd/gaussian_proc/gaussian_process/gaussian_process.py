@@ -1,7 +1,7 @@
 """Gaussian process user class (drop-in for
 gaussian_proc/gaussian_process/gaussian_process.py:21-71), with the prediction
-the reference leaves as a commented-out stub, and leave-one-out cross-validation
-of the fitted model."""
+the reference leaves as a commented-out stub, joint posterior draws at new points,
+and leave-one-out cross-validation of the fitted model."""
 
 import numpy
 
@@ -89,6 +89,73 @@ class GaussianProcess(object):
                                                         **kernel_params)
         mean, var = _predict_from_terms(c, q, G, X_star, sigma, sigma0, noise=noise)
         return (mean, var) if return_var else mean
+
+    def sample(self, test_points, X_star, size=1, seed=0, z=None, hyperparam=None, noise=False,
+               jitter=0.0, return_mean=False, xi=None, **kernel_params):
+        """``size`` joint draws of the posterior at ``test_points`` (n* x d) with basis
+        rows ``X_star`` (n* x m) -> (size, n*):
+          draw = mean + sigma (L xi),   xi ~ N(0, I),
+          L L^T = C0 + U U^T + (eta [noise] + jitter) I,   eta = (sigma0 / sigma)^2,
+        C0 + U U^T the joint covariance of ``predict(return_cov=True)`` in units of
+        sigma^2 (C0 = K** - K* S^-1 K*^T, U U^T = r (X^T S^-1 X)^-1 r^T) and mean its mean:
+        the draws have exactly the covariance ``predict`` reports, ``noise=True``
+        adding sigma0^2 on its diagonal. The covariance stays on the device, where it
+        is factored and multiplied with the normals (MixedCorrelation.
+        posterior_sample_terms). ``jitter`` (>= 0, in correlation units, default 0: none
+        is invented) is added to the diagonal before the factorization; a covariance
+        that is not numerically positive definite, such as that of duplicated test
+        points with ``noise=False``, raises numpy.linalg.LinAlgError, and ``jitter=`` or
+        ``noise=True`` are the remedies. The normals come from the device generator:
+        draw j is a function of (``seed``, j) alone (gaussian_proc._normal.
+        standard_normals states it); or ``xi`` (n* x size) supplies them.
+        ``z``, ``hyperparam`` and the kernel keywords are those of ``predict``.
+        -> draws, or (draws, mean) with ``return_mean``."""
+        if z is None:
+            z = self.z
+        if hyperparam is None and self.results is not None:
+            hyperparam = (self.results['sigma'], self.results['sigma0'])
+        if z is None or hyperparam is None:
+            raise ValueError('sample needs z and hyperparam=(sigma, sigma0), or an earlier '
+                             'train(z)')
+        bad = sorted(set(kernel_params) - {'points', 'correlation_scale', 'nu', 'cross',
+                                           'cross_star'})
+        if bad:
+            raise TypeError('sample: unexpected keyword argument %s' % ', '.join(map(repr, bad)))
+        sigma, sigma0 = float(hyperparam[0]), float(hyperparam[1])
+        if not sigma > 0.0:
+            raise ValueError('sigma must be positive')
+        size = int(size)
+        if size < 1:
+            raise ValueError('size must be at least 1')
+        jitter = float(jitter)
+        if not jitter >= 0.0:
+            raise ValueError('jitter must be non-negative')
+        X = numpy.asarray(self.X, dtype=float)
+        n, m = X.shape
+        z = numpy.asarray(z, dtype=float)
+        if z.shape != (n,):
+            raise ValueError('z must have %d entries' % n)
+        test_points = numpy.asarray(test_points, dtype=float)
+        if test_points.ndim != 2 or test_points.shape[0] < 1:
+            raise ValueError('test_points must be a 2D array (n*, dimension) with n* >= 1')
+        nstar = test_points.shape[0]
+        X_star = numpy.asarray(X_star, dtype=float)
+        if X_star.shape != (nstar, m):
+            raise ValueError('X_star must be %d x %d' % (nstar, m))
+        if xi is not None:
+            xi = numpy.asarray(xi, dtype=float)
+            if xi.shape != (nstar, size):
+                raise ValueError('xi must be %d x %d' % (nstar, size))
+        eta = (sigma0 / sigma) ** 2
+        c, G, draws = self.likelihood.K_mixed.posterior_sample_terms(
+            eta, X, z, size=size, test_points=test_points, X_star=X_star,
+            extra_eta=(eta if noise else 0.0) + jitter, seed=seed, first=0, xi=xi,
+            **kernel_params)
+        q = numpy.zeros(nstar)   # (the mean does not read q)
+        mean, _ = _predict_from_terms(c, q, G, X_star, sigma, sigma0, noise=noise)
+        draws *= sigma
+        draws += mean[None, :]
+        return (draws, mean) if return_mean else draws
 
     def _loo_args(self, z, hyperparam, who):
         """z and (sigma, sigma0), defaulting to the last train, checked. -> (X, z, sigma,

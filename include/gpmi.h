@@ -217,6 +217,53 @@ int gpmi_op_loo_terms(gpmi_op* op, double eta, double* dinv_out, double* sol_out
  * (when gpmi_op_set_timing is on). */
 int gpmi_op_loo_ms(gpmi_op* op, double* pass_ms, double* pass_bytes);
 
+/* ---------------------------------------------------------------- sampling --
+ * Like the prediction, an extension beyond the reference; serves
+ * gaussian_proc.GaussianProcess.sample and MixedCorrelation.sample of this build. */
+
+/* gpmi_op_predict_cov without the download of C0: the same launches, c_out, q_out
+ * and gram_out bit for bit those of gpmi_op_predict_cov (any may be NULL). C0 of the
+ * nstar points stays in the operator's covariance block, marked resident (as after
+ * gpmi_op_predict_cov) until the next covariance call replaces it, for
+ * gpmi_op_load_predict_cov. Status as gpmi_op_predict_cov. */
+int gpmi_op_predict_cov_resident(gpmi_op* op, double eta, const double* points, int d,
+                                 const double* scale, double nu, const double* test_points,
+                                 int64_t nstar, const double* kstar, int64_t ldks,
+                                 const double* kss, int64_t ldkss, double* c_out,
+                                 double* q_out, double* gram_out);
+
+/* K of dst <- C0 + U U^T, C0 the resident covariance of src's last covariance call
+ * (nstar points) and U the host block U[nstar][ldu] of m <= 15 columns (NULL with
+ * m = 0), without a host round trip of C0: one elementwise kernel on dst's stream after
+ * src's work, the update as sum over a ascending of fma(U[j][a], U[l][a], .), so that
+ * the result is exactly symmetric and, with m = 0, C0 bit for bit. The pad is the
+ * identity. Like gpmi_op_load_matrix it drops dst's cached factor.
+ * < 0: null handle, different devices, dst's size not nstar, no resident C0, m outside
+ * 0..15, ldu < m. */
+int gpmi_op_load_predict_cov(gpmi_op* dst, gpmi_op* src, const double* U, int64_t ldu,
+                             int m);
+
+/* nsamp draws of N(0, K + eta I): out[nsamp][ldout], row j = (L xi_j)^T with
+ * K + eta I = L L^T the cached factor (factorized if absent; no resident RHS needed).
+ * xi_j is column j of the host block xi[n][ldxi] when xi != NULL, else it is generated
+ * on the device for the global draw indices first .. first + nsamp: entry i of draw j
+ * is a function of (seed, j, i) alone (splitmix64 counters and Box-Muller;
+ * gaussian_proc/_normal.py restates it), whatever the chunking or nsamp. The product
+ * runs on fp64 MFMA in chunks of 1024 draws (GPMI_SAMPLE_CHUNK, a multiple of 128, read
+ * per call); within a chunk the triangular depth is cut into pieces chosen from the
+ * tile counts and the device's compute units (GPMI_SAMPLE_DEPTH, tile rows, overrides),
+ * summed in ascending order without atomics: the same call gives the same bits, and
+ * calls that differ in nsamp or the chunk width agree to rounding.
+ * > 0: first non-positive pivot; < 0: null handle, no matrix, nsamp < 1, ldout < n,
+ * ldxi < nsamp. */
+int gpmi_op_sample(gpmi_op* op, double eta, const double* xi, int64_t ldxi,
+                   unsigned long long seed, unsigned long long first, int64_t nsamp,
+                   double* out, int64_t ldout);
+/* HIP-event ms of the last gpmi_op_sample's normal generation and of its product
+ * (with the sum of the pieces), and the product's flops, summed over the chunks
+ * (when gpmi_op_set_timing is on; 0 otherwise). */
+int gpmi_op_sample_ms(gpmi_op* op, double* normal_ms, double* trmm_ms, double* trmm_flops);
+
 /* ------------------------------------------------------------------ sparse --
  * Tapered (compact-support) Matérn correlation in CSR on the device, and the
  * Krylov primitives of the sparse likelihood path. Replaces
