@@ -370,6 +370,35 @@ int traceinv_build_w(gpmi_op* op) {
   return 0;
 }
 
+int traceinv_build_ainv(gpmi_op* op) {
+  DenseTraceInv& ti = op->tinv;
+  if (ti.have & 2) return 0;
+  const int nt = op->nt;
+  const int64_t np = op->n_pad;
+  HIP_TRY(ti.Td.reserve((size_t)nt * TS * TS));
+  hipStream_t s = op->stream;
+  // T = W W^T over k-panels of 4 tiles; panel [p0, p0 + kd) updates tile rows I < imax
+  for (int p0 = 0; p0 < (int)np; p0 += 4 * TS) {
+    const int kd = std::min<int>(4 * TS, (int)np - p0);
+    const int imax = (p0 + kd) / TS;
+    hipLaunchKernelGGL(gram_panel_kernel, dim3(imax * (imax + 1) / 2), dim3(256), 0, s,
+                       ti.W, np, ti.Td, p0, kd, imax);
+    LAUNCH_CHECK("gram_panel_kernel");
+  }
+  hipLaunchKernelGGL(gram_sumsq_kernel, dim3(nt), dim3(256), 0, s, ti.W, np, ti.Td,
+                     ti.tpart);
+  LAUNCH_CHECK("gram_sumsq_kernel");
+  std::vector<double> h((size_t)nt);
+  HIP_TRY(hipMemcpyAsync(h.data(), ti.tpart, sizeof(double) * h.size(),
+                         hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  double acc = 0.0;
+  for (int q = 0; q < nt; ++q) acc += h[q];
+  ti.value[1] = acc - (double)(np - op->n);
+  ti.have |= 2;
+  return 0;
+}
+
 }  // namespace gpmi
 
 extern "C" {
@@ -469,33 +498,8 @@ int gpmi_op_traceinv(gpmi_op* op, double eta, int exponent, double* value) {
   if (rc) return rc;
   // W = L^-T from the cached factor in slot 0 (needed by both exponents)
   if ((rc = traceinv_build_w(op))) return rc;
-  DenseTraceInv& ti = op->tinv;
-  if (exponent == 2 && !(ti.have & 2)) {
-    const int nt = op->nt;
-    const int64_t np = op->n_pad;
-    HIP_TRY(ti.Td.reserve((size_t)nt * TS * TS));
-    hipStream_t s = op->stream;
-    // T = W W^T over k-panels of 4 tiles; panel [p0, p0 + kd) updates tile rows I < imax
-    for (int p0 = 0; p0 < (int)np; p0 += 4 * TS) {
-      const int kd = std::min<int>(4 * TS, (int)np - p0);
-      const int imax = (p0 + kd) / TS;
-      hipLaunchKernelGGL(gram_panel_kernel, dim3(imax * (imax + 1) / 2), dim3(256), 0, s,
-                         ti.W, np, ti.Td, p0, kd, imax);
-      LAUNCH_CHECK("gram_panel_kernel");
-    }
-    hipLaunchKernelGGL(gram_sumsq_kernel, dim3(nt), dim3(256), 0, s, ti.W, np, ti.Td,
-                       ti.tpart);
-    LAUNCH_CHECK("gram_sumsq_kernel");
-    std::vector<double> h((size_t)nt);
-    HIP_TRY(hipMemcpyAsync(h.data(), ti.tpart, sizeof(double) * h.size(),
-                           hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    double acc = 0.0;
-    for (int q = 0; q < nt; ++q) acc += h[q];
-    ti.value[1] = acc - (double)(np - op->n);
-    ti.have |= 2;
-  }
-  *value = ti.value[exponent - 1];
+  if (exponent == 2 && (rc = traceinv_build_ainv(op))) return rc;
+  *value = op->tinv.value[exponent - 1];
   return 0;
 }
 

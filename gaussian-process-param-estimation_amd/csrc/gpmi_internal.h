@@ -127,6 +127,18 @@ __global__ void loo_pass_kernel(const double* W, int64_t ldw, const double* Y, i
 __global__ void loo_reduce_kernel(const double* part, int64_t n_pad, int cw, int nchunk,
                                   double* out);
 
+// Correlation-scale gradient terms (gpmi_scale_grad.hip): one workgroup per lower tile of
+// A^-1 -> part[tile][1 + ncoef][8], reduced over the tiles in ascending order into
+// out[1 + ncoef][8]. mode: a closed form or MATERN_GAUSS; nc: ncoef rounded up to 0, 2 or
+// 4, the coefficient matrices coef[nc][16][16] the pass multiplies (zero beyond ncoef).
+constexpr int SG_MAX_COEF = 4;
+void launch_scale_grad_pass(hipStream_t s, int mode, int nc, const double* W, int64_t ldw,
+                            const double* Td, const double* sol, const double* coef, int ncoef,
+                            const double* points, int64_t n, int d, const double* scale, int nt,
+                            double* part);
+__global__ void scale_grad_reduce_kernel(const double* part, int ntile, int nval, int d,
+                                         const double* scale_dev, double* out);
+
 // Draws from the cached factor and the covariance hand-over (gpmi_sample.hip; work list in
 // gpmi_sample_plan.h).
 __global__ void sample_normal_kernel(double* Xi, int64_t ld, int64_t rows, int64_t cols,

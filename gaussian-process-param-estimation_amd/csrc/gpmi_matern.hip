@@ -16,6 +16,7 @@
 #include <stdint.h>
 
 #include "gpmi_internal.h"
+#include "gpmi_matern_dev.h"
 
 #ifndef GPMI_MATERN_NT
 #define GPMI_MATERN_NT 1
@@ -103,36 +104,7 @@ __device__ __forceinline__ double matern_value(double x, const MaternParams& P) 
   }
 }
 
-// (p_i - p_j) / scale, correctly rounded as the reference's division, from the
-// correctly rounded reciprocal rs = RN(1 / scale): q0 = RN(a rs), the exact
-// remainder a - q0 scale (FMA), q = RN(q0 + rem rs) (Markstein's final step:
-// RN(a / scale) whenever rs is within half an ulp of 1 / scale and q0 within one
-// ulp of a / scale, no overflow / underflow; 2e8 random cases checked equal on
-// the host). One multiply and two FMAs instead of the ~10-instruction IEEE
-// division sequence.
-__device__ __forceinline__ double div_by_scale(double a, double sc, double rs) {
-  const double q0 = a * rs;
-  const double rem = fma(-q0, sc, a);
-  return fma(rem, rs, q0);
-}
-
-// Scaled Euclidean distance, summed in dimension order (_kernels.pyx:130-136).
-// Unrolled to GPMI_MAX_DIM so p_j stays in registers.
-__device__ __forceinline__ double scaled_distance(const double* __restrict__ pi,
-                                                  const double (&pj)[GPMI_MAX_DIM],
-                                                  const double* __restrict__ scale,
-                                                  const double* __restrict__ rscale, int d) {
-#pragma clang fp contract(off)
-  double acc = 0.0;
-#pragma unroll
-  for (int k = 0; k < GPMI_MAX_DIM; ++k) {
-    if (k < d) {
-      const double v = div_by_scale(pi[k] - pj[k], scale[k], rscale[k]);
-      acc += v * v;
-    }
-  }
-  return sqrt(acc);
-}
+// (div_by_scale and scaled_distance: gpmi_matern_dev.h, shared with the scale gradient.)
 
 // One workgroup = one 64 x 64 tile (I >= J) of the lower triangle, the
 // blockIdx -> (I, J) map walks the tiles row by row. Every entry is evaluated

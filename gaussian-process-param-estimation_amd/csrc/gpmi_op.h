@@ -9,6 +9,7 @@
 //                           a factor (DenseFactor, DenseTiming, DenseTraceInv)
 //   gpmi_dense_predict.hip  the prediction terms and the joint covariance (DensePredict)
 //   gpmi_dense_loo.hip      the leave-one-out terms (DenseLoo)
+//   gpmi_dense_scale_grad.hip  the correlation-scale gradient terms (DenseScaleGrad)
 //   gpmi_dense_sample.hip   draws from the cached factor, and the hand-over of the joint
 //                           covariance to a second operator (DenseSample)
 // Every device buffer is a DevBuf, every stream and event an owner (gpmi_host.h):
@@ -83,6 +84,7 @@ struct DenseTiming {
   EventPool pred;          // begin, end of a prediction call; (begin, end) per trailing product
   EventPool cov;           // begin, end of the covariance's partial-product launch
   EventPool loo;           // begin, end of the leave-one-out pass over W
+  EventPool sgrad;         // begin, end of the scale gradient's pass over the tiles of A^-1
   EventPool samp;          // per chunk of draws: begin, end of the normals and of the product
   std::vector<std::pair<int, double>> syrk_log;  // (event index, flops)
   std::vector<std::array<int, 3>> syrk_shape;    // (w, t, kdim) per logged launch
@@ -97,7 +99,7 @@ struct DenseTraceInv {
   DevBuf<double> tpart;    // [nt * (nt + 1) / 2 + nt * nt] partials
   DevBuf<double> Td;       // [nt][128][128] diagonal tiles of A^-1 (exponent 2)
   uint64_t gen = ~0ull;    // the factor generation the cache is valid for
-  int have = 0;            // bit 0: tr(A^-1), bit 1: tr(A^-2)
+  int have = 0;            // bit 0: W and tr(A^-1), bit 1: the tiles of A^-1 and tr(A^-2)
   double value[2] = {0.0, 0.0};
 };
 
@@ -127,6 +129,17 @@ struct DensePredict {
 struct DenseLoo {
   DevBuf<double> part;     // [nchunk][n_pad][17] per-chunk partials
   DevBuf<double> out;      // [n_pad][17] (W Y)_i, then d_i
+  double last_ms = 0.0, last_bytes = 0.0;
+};
+
+// gpmi_op_scale_grad_terms: the points, scale and coefficient matrices of the call on the
+// device, and the per-tile partials (grown to the largest call so far).
+struct DenseScaleGrad {
+  DevBuf<double> pts;      // [n][d]
+  DevBuf<double> scale;    // [8]
+  DevBuf<double> coef;     // [4][16][16]
+  DevBuf<double> part;     // [nt (nt + 1) / 2][1 + ncoef][8]
+  DevBuf<double> out;      // [1 + ncoef][8]
   double last_ms = 0.0, last_bytes = 0.0;
 };
 
@@ -170,6 +183,7 @@ struct gpmi_op {
   gpmi::DenseTraceInv tinv;
   gpmi::DensePredict pred;
   gpmi::DenseLoo loo;
+  gpmi::DenseScaleGrad sgrad;
   gpmi::DenseSample samp;
 
   gpmi::BatchPtrs ptrs() const { return fac.ptrs(n_pad, nt); }
@@ -190,6 +204,15 @@ int forward_substitute(gpmi_op* op, const BatchPtrs& P);
 // W = L^-T of the cached factor in slot 0 into tinv.W, with tr((K + eta I)^-1) from the
 // same launches; nothing when tinv already holds them for this factorization.
 int traceinv_build_w(gpmi_op* op);
+// The lower tiles of A^-1 = W W^T (strict lower tiles in W's lower block triangle,
+// diagonal tiles in tinv.Td) and tr(A^-2) from them, after traceinv_build_w; nothing when
+// tinv already holds them for this factorization.
+int traceinv_build_ainv(gpmi_op* op);
+
+// gpmi_dense_loo.hip
+// loo.out [n_pad][17] <- row i of A^-1 rhs_src, then (A^-1)_ii, by the chunked pass over W
+// and its reduce (GPMI_LOO_CHUNK read per call), after traceinv_build_w.
+int loo_build_sol(gpmi_op* op);
 
 // gpmi_dense_predict.hip
 // Y = L^-1 rhs_src for the cached factor into pred.PY, and G = Y^T Y into pred.Pgram[0..256).

@@ -71,6 +71,11 @@ SIGNATURES = {
     'gpmi_op_loo_terms': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p, c_double_p, c_i64,
                                          c_double_p]),
     'gpmi_op_loo_ms': (ctypes.c_int, [c_op_p, c_double_p, c_double_p]),
+    'gpmi_op_scale_grad_terms': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p,
+                                                ctypes.c_int, c_double_p, ctypes.c_double,
+                                                c_double_p, ctypes.c_int, c_double_p,
+                                                c_double_p]),
+    'gpmi_op_scale_grad_ms': (ctypes.c_int, [c_op_p, c_double_p, c_double_p]),
     'gpmi_op_predict_cov_resident': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p,
                                                     ctypes.c_int, c_double_p, ctypes.c_double,
                                                     c_double_p, c_i64, c_double_p, c_i64,
@@ -547,6 +552,45 @@ class Operator(object):
         a, b = ctypes.c_double(), ctypes.c_double()
         check(self.lib.gpmi_op_loo_ms(self.h, ctypes.byref(a), ctypes.byref(b)),
               'gpmi_op_loo_ms')
+        return dict(pass_ms=a.value, pass_bytes=b.value)
+
+    def scale_grad_terms(self, eta, points, scale, nu, coef=None):
+        """-> (t[d], q[ncoef, d]) for the factor of A = K + eta I, K the Matérn
+        correlation of ``points`` (n x d) at ``scale`` (d) and ``nu``:
+        t_k = tr(A^-1 dK/d rho_k) and q_k(C) = sum_ij (Sol C Sol^T)_ij dK_ij/d rho_k with
+        Sol = A^-1 R for the resident RHS R and each symmetric C of ``coef``
+        (ncoef x nrhs x nrhs, ncoef <= 4; None: no C, and no RHS is needed)
+        (gpmi_op_scale_grad_terms): one pass over the lower tiles of A^-1, the ones
+        traceinv(eta, 2) forms and caches. nu must be 0.5, 1.5, 2.5 or >= 100."""
+        points = as_c(points)
+        scale = as_c(scale)
+        if points.ndim != 2 or points.shape[0] != self.n:
+            raise ValueError('points must be %d x d' % self.n)
+        d = points.shape[1]
+        if scale.shape != (d,):
+            raise ValueError('scale must have one entry per dimension (%d)' % d)
+        m = self.nrhs
+        if coef is None:
+            coef = numpy.empty((0, m, m))
+        coef = as_c(coef)
+        if coef.ndim != 3 or coef.shape[1:] != (m, m):
+            raise ValueError('coef must be ncoef x %d x %d' % (m, m))
+        nc = coef.shape[0]
+        t = numpy.zeros(d)
+        q = numpy.zeros((nc, d))
+        check(self.lib.gpmi_op_scale_grad_terms(self.h, float(eta), dptr(points), d, dptr(scale),
+                                                float(nu), dptr(coef) if nc else None, nc,
+                                                dptr(t), dptr(q) if nc else None),
+              'gpmi_op_scale_grad_terms')
+        return t, q
+
+    def scale_grad_ms(self):
+        """-> dict(pass_ms, pass_bytes): the pass over the tiles of A^-1 of the last
+        scale_grad_terms with set_timing(True) (HIP events; 0 without) and the bytes it
+        read."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        check(self.lib.gpmi_op_scale_grad_ms(self.h, ctypes.byref(a), ctypes.byref(b)),
+              'gpmi_op_scale_grad_ms')
         return dict(pass_ms=a.value, pass_bytes=b.value)
 
 

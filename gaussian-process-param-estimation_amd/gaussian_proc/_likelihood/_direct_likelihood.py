@@ -28,7 +28,7 @@ import numpy
 import scipy.optimize
 from functools import partial
 
-from ._profile_likelihood import _use_band
+from ._profile_likelihood import _use_band, _scale_grad_from_terms
 
 __all__ = ['DirectLikelihood']
 
@@ -222,6 +222,22 @@ class DirectLikelihood(object):
         jac = numpy.array([-0.5 * trace_KM + 0.5 * zMKMz,
                            -0.5 * trace_M + 0.5 * zMMz], dtype=float)
         return -jac if sign_switch else jac
+
+    @staticmethod
+    def log_likelihood_der1_scale(z, X, K_mixed, hyperparam, **kernel_params):
+        """Gradient of the direct likelihood at ``hyperparam = (sigma, sigma0)`` in the
+        correlation scale rho (one entry per point dimension), analytic: one
+        factorization and one fused device pass (MixedCorrelation.scale_grad_terms,
+        _scale_grad_from_terms). |sigma| below the small-sigma threshold, where the
+        likelihood does not depend on K, raises ValueError. ``kernel_params``: points,
+        correlation_scale and nu for an ndarray K. -> array (d)."""
+        sigma, sigma0 = float(hyperparam[0]), float(hyperparam[1])
+        if numpy.abs(sigma) < _TOL:
+            raise ValueError('the scale gradient needs |sigma| >= %g' % _TOL)
+        X = numpy.asarray(X, dtype=float)
+        n, m = X.shape
+        T = K_mixed.scale_grad_terms((sigma0 / sigma) ** 2, X, z, **kernel_params)
+        return _scale_grad_from_terms(n, m, T['t'], T['qX'], T['qc'], T['G'], sigma=sigma)
 
     @staticmethod
     def log_likelihood_hessian(z, X, K_mixed, sign_switch, hyperparam):    # :163-270

@@ -139,6 +139,68 @@ def _loo_from_terms(dinv, sol, G, z, sigma, sigma0, noise=True):
     return mean, var
 
 
+def _scale_grad_coef(G):
+    """The two symmetric coefficient matrices MixedCorrelation.scale_grad_terms hands to
+    the device, from G = R^T A^-1 R, R = [X z]: C_X = [[G_XX^-1, 0], [0, 0]] and c c^T with
+    c = [-a; 1], a = G_XX^-1 G_Xz (so that Sol c = P z). m = 0 leaves C_X = 0 and c = [1].
+    -> array (2, m + 1, m + 1)."""
+    G = numpy.asarray(G, dtype=float)
+    m = G.shape[0] - 1
+    if m < 0 or G.shape != (m + 1, m + 1):
+        raise ValueError('G must be (m + 1) x (m + 1)')
+    coef = numpy.zeros((2, m + 1, m + 1))
+    c = numpy.ones(m + 1)
+    if m > 0:
+        Bi = numpy.linalg.inv(G[:m, :m])
+        coef[0, :m, :m] = 0.5 * (Bi + Bi.T)
+        c[:m] = -numpy.linalg.solve(G[:m, :m], G[:m, m])
+    coef[1] = numpy.outer(c, c)
+    return coef
+
+
+def _scale_grad_from_terms(n, m, t, qX, qc, G, sigma=None):
+    """Gradient of the log-likelihood in the correlation scale rho (d entries) from the
+    terms of MixedCorrelation.scale_grad_terms. With A = K + eta I, dK_k = dK / d rho_k,
+    P = A^-1 - A^-1 X G_XX^-1 X^T A^-1 and w = P z:
+      t[k] = tr(A^-1 dK_k),  qX[k] = tr(A^-1 X G_XX^-1 X^T A^-1 dK_k),  qc[k] = w^T dK_k w,
+      tr(P dK_k) = t[k] - qX[k],   z^T P z = c^T G c,  c = [-G_XX^-1 G_Xz; 1].
+    ``sigma`` given: the direct likelihood at (sigma, sigma0 = sqrt(eta) sigma),
+      dl / d rho_k  = -tr(P dK_k) / 2 + w^T dK_k w / (2 sigma^2);
+    ``sigma`` None: the likelihood profiled over sigma (sigma^2 = z^T P z / (n - m)),
+      dlp / d rho_k = -tr(P dK_k) / 2 + (n - m) w^T dK_k w / (2 z^T P z).
+    -> array (d)."""
+    t = numpy.asarray(t, dtype=float)
+    qX = numpy.asarray(qX, dtype=float)
+    qc = numpy.asarray(qc, dtype=float)
+    G = numpy.asarray(G, dtype=float)
+    if G.shape != (m + 1, m + 1) or t.ndim != 1 or qX.shape != t.shape or qc.shape != t.shape:
+        raise ValueError('t, qX and qc must be d and G (m + 1) x (m + 1)')
+    if sigma is None:
+        zPz = G[m, m] - (G[:m, m] @ numpy.linalg.solve(G[:m, :m], G[:m, m]) if m > 0 else 0.0)
+        s = 0.5 * (n - m) / zPz
+    else:
+        if not abs(sigma) > 0.0:
+            raise ValueError('sigma must be non-zero')
+        s = 0.5 / sigma ** 2
+    return -0.5 * (t - qX) + s * qc
+
+
+def _eta_grad_from_terms(n, m, trinv, sol, G):
+    """d lp / d eta of the likelihood profiled over sigma, from the leave-one-out terms
+    (_scale_grad_from_terms with dA = I): -tr(P) / 2 + (n - m) w^T w / (2 z^T P z) with
+    tr(P) = tr(A^-1) - tr(G_XX^-1 U^T U), U = sol[:, :m], w = sol c. -> float."""
+    sol = numpy.asarray(sol, dtype=float)
+    G = numpy.asarray(G, dtype=float)
+    c = numpy.ones(m + 1)
+    trP = float(trinv)
+    if m > 0:
+        c[:m] = -numpy.linalg.solve(G[:m, :m], G[:m, m])
+        U = sol[:, :m]
+        trP -= float(numpy.trace(numpy.linalg.solve(G[:m, :m], U.T @ U)))
+    w = sol @ c
+    return -0.5 * trP + 0.5 * (n - m) * float(w @ w) / float(c @ G @ c)
+
+
 def _cross_validation_scores(z, mean, var):
     """The summary scores of GaussianProcess.cross_validate from the leave-one-out
     mean and (noisy) variance. -> dict."""
@@ -265,6 +327,18 @@ class ProfileLikelihood(object):
         _, G1, G2, G3, tr1 = K_mixed.der_terms(etas, X, z, traceinv=True)
         return numpy.array([_der_from_terms(n, m, G1[i], G2[i], G3[i], tr1[i])[0]
                             for i in range(etas.size)])
+
+    @staticmethod
+    def log_likelihood_der1_scale(z, X, K_mixed, eta, **kernel_params):
+        """Gradient of the likelihood profiled over sigma in the correlation scale rho
+        (one entry per point dimension) at ``eta``, analytic: one factorization and one
+        fused device pass (MixedCorrelation.scale_grad_terms, _scale_grad_from_terms),
+        not 2 d re-assemblies and factorizations. ``kernel_params``: points,
+        correlation_scale and nu for an ndarray K. -> array (d)."""
+        X = numpy.asarray(X, dtype=float)
+        n, m = X.shape
+        T = K_mixed.scale_grad_terms(eta, X, z, **kernel_params)
+        return _scale_grad_from_terms(n, m, T['t'], T['qX'], T['qc'], T['G'])
 
     @staticmethod
     def log_likelihood_der2_eta(z, X, K_mixed, eta):               # :138-192

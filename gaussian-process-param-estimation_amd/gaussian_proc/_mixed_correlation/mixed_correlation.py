@@ -148,6 +148,7 @@ class MixedCorrelation(object):
             self.op = _hip.Operator(K.shape[0], device=device, max_batch=max_batch or 1)
             self.op.load_matrix(K)
         self.n = self.op.n
+        self._k_gen = self.op.generation
         self._trace_cache = None
         self._rhs_cache = None
         self._band = None
@@ -229,10 +230,28 @@ class MixedCorrelation(object):
 
     # ---- 'eigenvalue': one-time band reduction -----------------------------
 
+    def _k_changed(self):
+        """Drop what was cached from K if the dense operator's K has been replaced since
+        (DeviceCorrelation.set_correlation_scale re-assembles it in place): the traces,
+        the band form and its right-hand sides, the eigenvalues, the eta-derivative
+        cache; an interpolant is rebuilt. The operator itself drops its factor on
+        assembly, and the resident right-hand sides stay valid."""
+        if self.sparse or self.op is None or self.op.generation == self._k_gen:
+            return
+        self._k_gen = self.op.generation
+        self._trace_cache = None
+        self._band = None
+        self._band_rhs = None
+        self._eig = None
+        self._der_cache = None
+        if self.interpolate:
+            self._build_interpolant()
+
     def eigenvalues(self):
         """Eigenvalues of K (ascending), the reference's K_eigenvalues
         (mixed_correlation.py:76-79): band form on the device, then bulge
         chasing to tridiagonal and bisection (computed once, on first use)."""
+        self._k_changed()
         if self._eig is None:
             self._eig = self.band().eigenvalues()
         return self._eig
@@ -243,6 +262,7 @@ class MixedCorrelation(object):
         device: K = Q B Q^T with B banded (bandwidth 128), computed on first use.
         Afterwards logdet(eta) and the likelihood terms cost one banded Cholesky
         of B + eta I per eta (csrc/gpmi_band.hip)."""
+        self._k_changed()
         if self._band is None:
             self._band = _hip.Band(self._dense())
         return self._band
@@ -557,6 +577,7 @@ class MixedCorrelation(object):
     def _traces(self):
         if self.sparse:
             return self._sparse_traces()
+        self._k_changed()
         if self._trace_cache is None:
             self._trace_cache = self.op.trace()
         return self._trace_cache
@@ -584,6 +605,7 @@ class MixedCorrelation(object):
         raise ValueError('Existing methods are "exact", "eigenvalue", and "slq".')
 
     def traceinv(self, eta, exponent=1):                           # :155-215
+        self._k_changed()
         if self.interpolate:
             # :167-170: the interpolant of tr((K + eta I)^-1), whatever the exponent
             return self.interpolate_traceinv.interpolate(eta)
@@ -616,6 +638,7 @@ class MixedCorrelation(object):
         return float(numpy.trace(numpy.linalg.matrix_power(Ainv, exponent)))
 
     def logdet(self, eta, exponent=1):                             # :221-274
+        self._k_changed()
         if self.imate_method == 'slq' and self.sop is not None:
             return exponent * self._slq(eta, 'logdet')
         if self.imate_method not in ('eigenvalue', 'cholesky', 'hutchinson'):
@@ -742,6 +765,57 @@ class MixedCorrelation(object):
             raise ValueError('X must be %d x m' % self.n)
         self.set_rhs(X, z)
         return self.op.loo_terms(eta)
+
+    def scale_grad_terms(self, eta, X, z, points=None, correlation_scale=None, nu=None):
+        """The device terms of the likelihood's gradient in the correlation scale rho
+        (d entries) of a Matérn K (the reference has no counterpart). With A = K + eta I,
+        R = [X z], Sol = A^-1 R, G = R^T Sol, a = G_XX^-1 G_Xz, c = [-a; 1] and
+        dK_k = dK / d rho_k:
+          t[k]  = tr(A^-1 dK_k)
+          qX[k] = tr(A^-1 X G_XX^-1 X^T A^-1 dK_k)     so tr(P dK_k) = t[k] - qX[k]
+          qc[k] = w^T dK_k w,  w = Sol c = P z
+        with P = A^-1 - A^-1 X G_XX^-1 X^T A^-1. One dense Cholesky of A (cached per eta),
+        its triangular inverse, the tiles of A^-1 = W W^T (those traceinv(eta, 2) forms)
+        and one fused pass that builds dK_k entry by entry from the point coordinates
+        (csrc/gpmi_scale_grad.hip); _scale_grad_from_terms turns the terms into the
+        gradient. Kernel parameters default to those of a DeviceCorrelation K and are
+        required (``points``, ``correlation_scale``, ``nu``) for an ndarray K, which must
+        be the Matérn matrix of exactly those. A sparse K, or a nu other than 0.5, 1.5,
+        2.5 or >= 100, raises NotImplementedError; K + eta I not positive definite raises
+        numpy.linalg.LinAlgError. Returns dict(t, qX, qc, trinv = tr(A^-1) as the sum of
+        the leave-one-out pass's diagonal, sol, G)."""
+        from .._likelihood._profile_likelihood import _scale_grad_coef
+        if self.sparse:
+            raise NotImplementedError('the scale gradient on a sparse K is not implemented')
+        X = numpy.asarray(X, dtype=float)
+        if X.ndim != 2 or X.shape[0] != self.n:
+            raise ValueError('X must be %d x m' % self.n)
+        if isinstance(self.K, DeviceCorrelation):
+            points = self.K.points if points is None else points
+            correlation_scale = self.K.correlation_scale if correlation_scale is None \
+                else correlation_scale
+            nu = self.K.nu if nu is None else nu
+        if points is None or correlation_scale is None or nu is None:
+            raise ValueError('an ndarray K needs points, correlation_scale and nu')
+        points = numpy.ascontiguousarray(points, dtype=float)
+        if points.ndim != 2 or points.shape[0] != self.n:
+            raise ValueError('points must be %d x d' % self.n)
+        if numpy.isscalar(correlation_scale):
+            correlation_scale = numpy.repeat(float(correlation_scale), points.shape[1])
+        correlation_scale = numpy.asarray(correlation_scale, dtype=float).ravel()
+        if correlation_scale.size != points.shape[1]:
+            raise ValueError('correlation_scale must be a scalar or have one entry per '
+                             'dimension (%d)' % points.shape[1])
+        nu = float(nu)
+        if nu not in (0.5, 1.5, 2.5) and nu < 100.0:
+            raise NotImplementedError('the scale gradient needs nu = 0.5, 1.5, 2.5 or >= 100 '
+                                      '(got %g)' % nu)
+        self.set_rhs(X, z)
+        dinv, sol, G = self.op.loo_terms(eta)
+        t, q = self.op.scale_grad_terms(eta, points, correlation_scale, nu,
+                                        _scale_grad_coef(G))
+        return {'t': t, 'qX': q[0], 'qc': q[1], 'trinv': float(numpy.sum(dinv)), 'sol': sol,
+                'G': G}
 
     def sample(self, eta, size=1, seed=0, first=0, xi=None):
         """Draws of N(0, K + eta I) for a dense K (the reference has no counterpart):

@@ -33,6 +33,124 @@ class GaussianProcess(object):
         self.z = numpy.asarray(z, dtype=float).copy()
         self.results = results
 
+    def scale_gradient(self, z=None, hyperparam=None, **kernel_params):
+        """Gradient of the (direct, restricted) log-likelihood at
+        ``hyperparam = (sigma, sigma0)`` in the correlation scale of K, one entry per
+        point dimension, analytic (DirectLikelihood.log_likelihood_der1_scale). ``z``
+        and ``hyperparam`` default to those of the last ``train`` or ``train_scale``;
+        an ndarray K needs ``points``, ``correlation_scale`` and ``nu`` as keywords.
+        -> array (d)."""
+        from .._likelihood._direct_likelihood import DirectLikelihood
+        if z is None:
+            z = self.z
+        if hyperparam is None and self.results is not None:
+            hyperparam = (self.results['sigma'], self.results['sigma0'])
+        if z is None or hyperparam is None:
+            raise ValueError('scale_gradient needs z and hyperparam=(sigma, sigma0), or an '
+                             'earlier train(z)')
+        bad = sorted(set(kernel_params) - {'points', 'correlation_scale', 'nu'})
+        if bad:
+            raise TypeError('scale_gradient: unexpected keyword argument %s'
+                            % ', '.join(map(repr, bad)))
+        X = numpy.asarray(self.X, dtype=float)
+        z = numpy.asarray(z, dtype=float)
+        if z.shape != (X.shape[0],):
+            raise ValueError('z must have %d entries' % X.shape[0])
+        return DirectLikelihood.log_likelihood_der1_scale(z, X, self.likelihood.K_mixed,
+                                                          hyperparam, **kernel_params)
+
+    def train_scale(self, z, correlation_scale0=None, eta0=1.0, bounds=None, maxiter=100,
+                    tol=1e-6):
+        """Fit the correlation scale rho (one entry per point dimension) together with
+        eta = (sigma0 / sigma)^2 by maximizing the likelihood profiled over sigma, on a
+        device-resident K (a DeviceCorrelation; TypeError otherwise). L-BFGS-B over
+        theta = (ln eta, ln rho_1 .. ln rho_d) with the analytic gradient (chain rule
+        eta d/d eta, rho_k d/d rho_k): per evaluation K is re-assembled in place at rho
+        (DeviceCorrelation.set_correlation_scale) and factorized once, on a 'cholesky'
+        MixedCorrelation that drops what it cached from the old K. The start is
+        ``correlation_scale0`` (default: K's scale) and ``eta0``; ``bounds`` =
+        ((eta_lo, eta_hi), (rho_lo, rho_hi) per dimension) defaults to eta in
+        [1e-6, 1e3] and rho_k in [1e-2, 10] times the range of the points in dimension
+        k; ``tol`` is the projected-gradient tolerance (1e-3 ``tol`` the relative decrease
+        of the likelihood that also ends the search). Leaves K at the fitted scale,
+        rebuilds ``self.likelihood`` on it and keeps z and the results dict (sigma,
+        sigma0, eta, correlation_scale, max_lp, iterations, evaluations, success), printed
+        as ``train`` prints its own: ``predict``, ``sample`` and ``leave_one_out`` then
+        work unchanged."""
+        import scipy.optimize
+        from ..generate_correlation.generate_correlation import DeviceCorrelation, \
+            _broadcast_scale
+        from .._mixed_correlation import MixedCorrelation
+        from .._likelihood._profile_likelihood import _scale_grad_from_terms, \
+            _eta_grad_from_terms
+        K = self.K
+        if not isinstance(K, DeviceCorrelation):
+            raise TypeError('train_scale needs a device-resident K (generate_correlation(..., '
+                            'device_resident=True)), whose scale it can re-assemble')
+        X = numpy.asarray(self.X, dtype=float)
+        n, m = X.shape
+        z = numpy.asarray(z, dtype=float)
+        if z.shape != (n,):
+            raise ValueError('z must have %d entries' % n)
+        d = K.points.shape[1]
+        rho0 = K.correlation_scale if correlation_scale0 is None else \
+            _broadcast_scale(K.points, correlation_scale0)
+        rho0 = numpy.array(rho0, dtype=float)
+        if not (numpy.all(rho0 > 0.0) and eta0 > 0.0):
+            raise ValueError('correlation_scale0 and eta0 must be positive')
+        if bounds is None:
+            span = numpy.ptp(K.points, axis=0)
+            span = numpy.where(span > 0.0, span, 1.0)
+            bounds = [(1e-6, 1e3)] + [(1e-2 * s, 10.0 * s) for s in span]
+        bounds = [(float(lo), float(hi)) for lo, hi in bounds]
+        if len(bounds) != d + 1 or not all(0.0 < lo < hi for lo, hi in bounds):
+            raise ValueError('bounds must be %d pairs 0 < lo < hi (eta, then one per dimension)'
+                             % (d + 1))
+        log_bounds = [(numpy.log(lo), numpy.log(hi)) for lo, hi in bounds]
+        mc = MixedCorrelation(K, imate_method='cholesky')
+        count = [0]
+
+        def terms(theta):
+            eta, rho = float(numpy.exp(theta[0])), numpy.exp(theta[1:])
+            K.set_correlation_scale(rho)
+            ld, G = mc.loglik_terms([eta], X, z)
+            ld, G = float(ld[0]), G[0]
+            zPz = G[m, m] - (G[:m, m] @ numpy.linalg.solve(G[:m, :m], G[:m, m]) if m else 0.0)
+            logdet_B = numpy.linalg.slogdet(G[:m, :m])[1] if m else 0.0
+            s2 = zPz / (n - m)
+            lp = -0.5 * (n - m) * numpy.log(s2) - 0.5 * ld - 0.5 * logdet_B - 0.5 * (n - m)
+            return eta, rho, lp, s2
+
+        def fun(theta):
+            count[0] += 1
+            eta, rho, lp, _ = terms(theta)
+            T = mc.scale_grad_terms(eta, X, z)
+            g_rho = _scale_grad_from_terms(n, m, T['t'], T['qX'], T['qc'], T['G'])
+            g_eta = _eta_grad_from_terms(n, m, T['trinv'], T['sol'], T['G'])
+            return -lp, -numpy.concatenate([[eta * g_eta], rho * g_rho])
+
+        theta0 = numpy.concatenate([[numpy.log(eta0)], numpy.log(rho0)])
+        theta0 = numpy.clip(theta0, [b[0] for b in log_bounds], [b[1] for b in log_bounds])
+        res = scipy.optimize.minimize(fun, theta0, jac=True, method='L-BFGS-B',
+                                      bounds=log_bounds,
+                                      options={'maxiter': int(maxiter), 'gtol': float(tol),
+                                               'ftol': 1e-3 * float(tol)})
+        eta, rho, lp, s2 = terms(res.x)
+        # K is left as a new DeviceCorrelation at the fitted scale would be, without the
+        # factor of the last evaluation: what follows (predict, ...) then computes, bit
+        # for bit, what it computes on a GaussianProcess built at that scale
+        K.set_correlation_scale(rho)
+        sigma = float(numpy.sqrt(s2))
+        self.likelihood = Likelihood(self.X, K, likelihood_method=self.likelihood.likelihood_method,
+                                     device=K.device)
+        results = {'sigma': sigma, 'sigma0': float(numpy.sqrt(eta)) * sigma, 'eta': eta,
+                   'correlation_scale': numpy.array(rho), 'max_lp': float(lp),
+                   'iterations': int(res.nit), 'evaluations': int(count[0]),
+                   'success': bool(res.success)}
+        print(results)
+        self.z = z.copy()
+        self.results = results
+
     def predict(self, test_points, X_star, z=None, hyperparam=None, noise=False,
                 return_var=True, return_cov=False, **kernel_params):
         """Posterior mean (and variance) at ``test_points`` (n* x d) with basis rows

@@ -40,6 +40,19 @@ class DeviceCorrelation(object):
         """Copy K to the host."""
         return self.op.get_matrix()
 
+    def set_correlation_scale(self, correlation_scale):
+        """Re-assemble K in place, in the same operator, at another correlation scale (a
+        scalar or one entry per dimension): bit for bit the K of a new DeviceCorrelation
+        at that scale. The assembly drops the operator's cached factor, and a
+        MixedCorrelation over this object drops what it had cached from the old K (its
+        traces, band form, eigenvalues) at its next call; the resident right-hand sides
+        stay."""
+        scale = _broadcast_scale(self.points, correlation_scale)
+        if not numpy.all(scale > 0.0):
+            raise ValueError('correlation_scale must be positive')
+        self.op.assemble_matern(self.points, scale, self.nu)
+        self.correlation_scale = _hip.as_c(scale)
+
 
 class DeviceSparseCorrelation(object):
     """A tapered (compact-support) Matérn correlation kept on one GPU in CSR:

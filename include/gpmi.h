@@ -217,6 +217,37 @@ int gpmi_op_loo_terms(gpmi_op* op, double eta, double* dinv_out, double* sol_out
  * (when gpmi_op_set_timing is on). */
 int gpmi_op_loo_ms(gpmi_op* op, double* pass_ms, double* pass_bytes);
 
+/* ---------------------------------------------- correlation-scale gradient --
+ * Like the prediction, an extension beyond the reference; serves
+ * gaussian_proc's log_likelihood_der1_scale, GaussianProcess.scale_gradient and
+ * train_scale of this build. */
+
+/* The terms of the likelihood's gradient in the correlation scale rho (d entries)
+ * of a Matérn K, from the cached factor of A = K + eta I (factorized if absent).
+ * With u_k = (p_i - p_j)_k / rho_k, x = |u| and h(x) = -M'(x) / x,
+ *   dK_ij / d rho_k = h(x) u_k^2 / rho_k            (0 on the diagonal),
+ * and, with Sol = A^-1 R for the resident RHS block R,
+ *   tr_out[k]          = sum_ij (A^-1)_ij            dK_ij / d rho_k = tr(A^-1 dK_k)
+ *   quad_out[c * d + k] = sum_ij (Sol C_c Sol^T)_ij dK_ij / d rho_k
+ * for the ncoef (0..4) symmetric matrices coef[c][nrhs][nrhs]. dK is never
+ * formed: one pass reads the lower tiles of A^-1 = W W^T (those
+ * gpmi_op_traceinv(.., 2) forms and caches per factorization; either call reuses
+ * the other's), forms Sol C_c Sol^T tile by tile on fp64 MFMA from the
+ * leave-one-out pass's Sol, and evaluates h from points[n][d], scale[d] and nu,
+ * which must be those K was assembled with. Per-tile sums are added in
+ * ascending tile order (no atomics: the same input gives the same bits).
+ * tr_out and quad_out may be NULL. nu must be 0.5, 1.5, 2.5 or >= 100 (the
+ * Gaussian limit).
+ * > 0: first non-positive pivot; < 0: null handle (-1006), no matrix (-1000),
+ * ncoef outside 0..4 (-1030), ncoef > 0 without a resident RHS (-1012), d outside
+ * 1..8 (-1003), a null argument (-1004), a general nu (-1031). */
+int gpmi_op_scale_grad_terms(gpmi_op* op, double eta, const double* points, int d,
+                             const double* scale, double nu, const double* coef, int ncoef,
+                             double* tr_out, double* quad_out);
+/* HIP-event ms of the last call's pass over the tiles and the bytes of A^-1 it
+ * read (when gpmi_op_set_timing is on). */
+int gpmi_op_scale_grad_ms(gpmi_op* op, double* pass_ms, double* pass_bytes);
+
 /* ---------------------------------------------------------------- sampling --
  * Like the prediction, an extension beyond the reference; serves
  * gaussian_proc.GaussianProcess.sample and MixedCorrelation.sample of this build. */
