@@ -270,7 +270,7 @@ int gpmi_op_load_matrix(gpmi_op* op, const double* K_host, int64_t ldk) {
   }
   HIP_TRY(hipStreamSynchronize(op->stream));
   op->has_K = true;
-  op->fac.cache_valid = false;
+  op->fac.drop();
   return 0;
 }
 
@@ -290,7 +290,7 @@ int gpmi_op_load_sparse(gpmi_op* op, const gpmi_sp* sp) {
   }
   HIP_TRY(hipStreamSynchronize(op->stream));
   op->has_K = true;
-  op->fac.cache_valid = false;
+  op->fac.drop();
   return 0;
 }
 
@@ -301,7 +301,7 @@ int gpmi_op_assemble_matern(gpmi_op* op, const double* points, int d, const doub
                     op->n_pad);
   if (rc) return rc;
   op->has_K = true;
-  op->fac.cache_valid = false;
+  op->fac.drop();
   return 0;
 }
 

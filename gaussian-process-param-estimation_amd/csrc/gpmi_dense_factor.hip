@@ -2,7 +2,7 @@
 // batched factorization of K + eta_b I (launch list: gpmi_dense_plan.h; kernels in
 // gpmi_chol.hip, gpmi_diag.hip), its HIP-event timing, the cached single-eta factor,
 // and the entry points that consume a factor: loglik_batch, logdet, solve, traceinv
-// (kernels in gpmi_trinv.hip).
+// (kernels in gpmi_trinv.hip), and the read-backs of L, W = L^-T and A^-1 (tests).
 
 #include <hip/hip_runtime.h>
 
@@ -177,6 +177,7 @@ int run_factor(gpmi_op* op, const double* etas_host, int nb, const double* rhs_d
   op->tim.syrk_shape.clear();
   op->tim.colpanel_used = 0;
   op->fac.cache_valid = false;
+  op->fac.last_nb = 0;
   ++op->factor_gen;
   // slot 0 of R ends as L^-1 rhs_src only when that block is what is factored along
   op->pred.ry_gen = rhs_dev == op->rhs_src ? op->factor_gen : ~0ull;
@@ -222,6 +223,7 @@ int run_factor(gpmi_op* op, const double* etas_host, int nb, const double* rhs_d
   hipLaunchKernelGGL(finalize_kernel, dim3(nb), dim3(256), 0, s, P, nt, op->fac.out, OUT_LD);
   LAUNCH_CHECK("finalize_kernel");
   if (op->tim.on) HIP_TRY(hipEventRecord(op->tim.span[1], s));
+  op->fac.last_nb = nb;
   return 0;
 }
 
@@ -500,6 +502,79 @@ int gpmi_op_traceinv(gpmi_op* op, double eta, int exponent, double* value) {
   if ((rc = traceinv_build_w(op))) return rc;
   if (exponent == 2 && (rc = traceinv_build_ainv(op))) return rc;
   *value = op->tinv.value[exponent - 1];
+  return 0;
+}
+
+// The read-backs below launch no kernel and change no cache state: a copy on the
+// operator's stream, a synchronisation, and the masking on the host.
+
+int gpmi_op_get_factor(gpmi_op* op, int slot, double* L_out, int64_t ldl) {
+  if (!op) return set_errorf(-1006, "null handle");
+  if (!L_out) return set_errorf(-1004, "null output");
+  if (ldl < op->n) return set_errorf(-1005, "ldl %lld < n", (long long)ldl);
+  const DenseFactor& f = op->fac;
+  if (!op->has_K || f.last_nb < 1)
+    return set_errorf(-1032, "no factorization since the matrix was loaded");
+  if (slot < 0 || slot >= f.last_nb)
+    return set_errorf(-1033, "slot %d outside the last batch [0, %d)", slot, f.last_nb);
+  if (slot == 0 && !f.cache_valid) return set_errorf(-1032, "slot 0 holds no valid factor");
+  DeviceGuard g(op->device);
+  const int64_t n = op->n, np = op->n_pad;
+  int inf = 0;
+  HIP_TRY(hipMemcpyAsync(&inf, f.info + slot, sizeof(int), hipMemcpyDeviceToHost, op->stream));
+  HIP_TRY(hipStreamSynchronize(op->stream));
+  if (inf) return set_errorf(-1032, "slot %d: not positive definite (pivot %d)", slot, inf);
+  HIP_TRY(hipMemcpy2DAsync(L_out, sizeof(double) * ldl, f.A + (int64_t)slot * np * np,
+                           sizeof(double) * np, sizeof(double) * n, n, hipMemcpyDeviceToHost,
+                           op->stream));
+  HIP_TRY(hipStreamSynchronize(op->stream));
+  // the strictly upper tiles hold working data
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t j = i + 1; j < n; ++j) L_out[i * ldl + j] = 0.0;
+  return 0;
+}
+
+int gpmi_op_get_trinv(gpmi_op* op, double* W_out, int64_t ldw) {
+  if (!op) return set_errorf(-1006, "null handle");
+  if (!W_out) return set_errorf(-1004, "null output");
+  if (ldw < op->n) return set_errorf(-1005, "ldw %lld < n", (long long)ldw);
+  const DenseTraceInv& ti = op->tinv;
+  if (!op->fac.cache_valid || ti.gen != op->factor_gen || !(ti.have & 1))
+    return set_errorf(-1034, "no triangular inverse of the current factor (traceinv first)");
+  DeviceGuard g(op->device);
+  const int64_t n = op->n, np = op->n_pad;
+  HIP_TRY(hipMemcpy2DAsync(W_out, sizeof(double) * ldw, ti.W, sizeof(double) * np,
+                           sizeof(double) * n, n, hipMemcpyDeviceToHost, op->stream));
+  HIP_TRY(hipStreamSynchronize(op->stream));
+  // the lower block triangle may hold tiles of A^-1
+  for (int64_t i = TS; i < n; ++i)
+    for (int64_t j = 0; j < i / TS * TS; ++j) W_out[i * ldw + j] = 0.0;
+  return 0;
+}
+
+int gpmi_op_get_inverse(gpmi_op* op, double* Ainv_out, int64_t lda) {
+  if (!op) return set_errorf(-1006, "null handle");
+  if (!Ainv_out) return set_errorf(-1004, "null output");
+  if (lda < op->n) return set_errorf(-1005, "lda %lld < n", (long long)lda);
+  const DenseTraceInv& ti = op->tinv;
+  if (!op->fac.cache_valid || ti.gen != op->factor_gen || !(ti.have & 2))
+    return set_errorf(-1035, "no inverse of the current factor (traceinv, exponent 2, first)");
+  DeviceGuard g(op->device);
+  const int64_t n = op->n, np = op->n_pad;
+  std::vector<double> td((size_t)op->nt * TS * TS);
+  HIP_TRY(hipMemcpy2DAsync(Ainv_out, sizeof(double) * lda, ti.W, sizeof(double) * np,
+                           sizeof(double) * n, n, hipMemcpyDeviceToHost, op->stream));
+  HIP_TRY(hipMemcpyAsync(td.data(), ti.Td, sizeof(double) * td.size(), hipMemcpyDeviceToHost,
+                         op->stream));
+  HIP_TRY(hipStreamSynchronize(op->stream));
+  // strictly lower tiles as they are; the lower triangle of a diagonal tile from Td
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t c0 = i / TS * TS;
+    const double* row = td.data() + (size_t)c0 * TS + (i - c0) * TS;
+    for (int64_t j = c0; j <= i; ++j) Ainv_out[i * lda + j] = row[j - c0];
+  }
+  for (int64_t i = 0; i < n; ++i)
+    for (int64_t j = i + 1; j < n; ++j) Ainv_out[i * lda + j] = Ainv_out[j * lda + i];
   return 0;
 }
 

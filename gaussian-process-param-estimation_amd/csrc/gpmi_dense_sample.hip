@@ -76,7 +76,7 @@ int gpmi_op_load_predict_cov(gpmi_op* dst, gpmi_op* src, const double* U, int64_
   LAUNCH_CHECK("cov_lowrank_kernel");
   HIP_TRY(hipStreamSynchronize(s));
   dst->has_K = true;
-  dst->fac.cache_valid = false;
+  dst->fac.drop();
   return 0;
 }
 

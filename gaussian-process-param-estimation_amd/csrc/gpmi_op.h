@@ -59,6 +59,15 @@ struct DenseFactor {
   // factor cache: batch slot 0 holds the factor of K + cached_eta I
   bool cache_valid = false;
   double cached_eta = 0.0;
+  // members of the last factorization of the current K (0: none since K was loaded);
+  // slots 1 .. last_nb - 1 hold their factors until the next one (gpmi_op_get_factor)
+  int last_nb = 0;
+
+  // K changed: no slot holds a factor of it.
+  void drop() {
+    cache_valid = false;
+    last_nb = 0;
+  }
 
   BatchPtrs ptrs(int64_t n_pad, int nt) const {
     BatchPtrs p;

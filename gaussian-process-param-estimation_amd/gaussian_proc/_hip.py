@@ -40,6 +40,9 @@ SIGNATURES = {
     'gpmi_op_assemble_matern': (ctypes.c_int, [c_op_p, c_double_p, ctypes.c_int, c_double_p,
                                                ctypes.c_double]),
     'gpmi_op_get_matrix': (ctypes.c_int, [c_op_p, c_double_p, c_i64]),
+    'gpmi_op_get_factor': (ctypes.c_int, [c_op_p, ctypes.c_int, c_double_p, c_i64]),
+    'gpmi_op_get_trinv': (ctypes.c_int, [c_op_p, c_double_p, c_i64]),
+    'gpmi_op_get_inverse': (ctypes.c_int, [c_op_p, c_double_p, c_i64]),
     'gpmi_op_set_rhs': (ctypes.c_int, [c_op_p, c_double_p, c_i64, ctypes.c_int]),
     'gpmi_op_loglik_batch': (ctypes.c_int, [c_op_p, c_double_p, ctypes.c_int, c_double_p,
                                             c_double_p, c_int_p]),
@@ -287,6 +290,31 @@ class Operator(object):
         K = numpy.empty((self.n, self.n))
         check(self.lib.gpmi_op_get_matrix(self.h, dptr(K), self.n), 'gpmi_op_get_matrix')
         return K
+
+    def _readback(self, name, *lead, ld=None):
+        """An n x n read-back (tests, diagnostics) into the first n columns of an
+        n x ld buffer filled with NaN; the view of those columns is returned."""
+        ld = self.n if ld is None else int(ld)
+        buf = numpy.full((self.n, ld), numpy.nan)
+        check(getattr(self.lib, name)(self.h, *lead, dptr(buf), ld), name)
+        return buf[:, :self.n] if ld == self.n else buf
+
+    def factor(self, slot=0, ld=None):
+        """The lower-triangular factor L of K + eta I in batch slot ``slot`` of the last
+        factorization (gpmi_op_get_factor): slot 0 is the cached factor, slots >= 1 the
+        other members directly after a loglik_batch. With ``ld`` > n the whole n x ld
+        buffer comes back (its extra columns untouched, NaN)."""
+        return self._readback('gpmi_op_get_factor', int(slot), ld=ld)
+
+    def trinv(self, ld=None):
+        """W = L^-T of the cached factor, upper triangular, after traceinv
+        (gpmi_op_get_trinv)."""
+        return self._readback('gpmi_op_get_trinv', ld=ld)
+
+    def inverse(self, ld=None):
+        """(K + eta I)^-1 of the cached factor, exactly symmetric, after
+        traceinv(eta, 2) (gpmi_op_get_inverse)."""
+        return self._readback('gpmi_op_get_inverse', ld=ld)
 
     def set_rhs(self, R):
         R = rhs_block(R, self.n)

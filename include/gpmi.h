@@ -77,6 +77,26 @@ int gpmi_op_assemble_matern(gpmi_op* op, const double* points, int d,
                             const double* scale, double nu);
 /* Copy K back to the host ([n][ldk]). */
 int gpmi_op_get_matrix(gpmi_op* op, double* K_out, int64_t ldk);
+/* Read-backs of the dense path's intermediates (tests, diagnostics). Each copies
+ * on the operator's stream and synchronises; none launches a kernel or changes a
+ * cache. < 0: null handle or output, ld < n, or the state named below is absent
+ * (nothing is written then).
+ * The n x n lower-triangular factor L of K + eta_slot I in batch slot `slot` of the
+ * last factorization ([n][ldl]; the strict upper triangle is written as zeros).
+ * Slot 0 is the cached factor (gpmi_op_logdet, _solve, _traceinv, ... or member 0 of
+ * gpmi_op_loglik_batch); slots >= 1 hold the other members of a gpmi_op_loglik_batch
+ * until the next factorization. Refused when K was loaded or assembled since, when
+ * slot is outside the last batch, or when that member's info is non-zero. */
+int gpmi_op_get_factor(gpmi_op* op, int slot, double* L_out, int64_t ldl);
+/* W = L^-T of the cached factor ([n][ldw], upper triangular; the lower block
+ * triangle is written as zeros), after gpmi_op_traceinv (or gpmi_op_loo_terms,
+ * gpmi_op_scale_grad_terms) on the current factorization. */
+int gpmi_op_get_trinv(gpmi_op* op, double* W_out, int64_t ldw);
+/* (K + eta I)^-1 = W W^T of the cached factor, full and exactly symmetric
+ * ([n][lda]: the lower tiles the device holds, mirrored), after
+ * gpmi_op_traceinv(.., 2) (or gpmi_op_scale_grad_terms) on the current
+ * factorization. */
+int gpmi_op_get_inverse(gpmi_op* op, double* Ainv_out, int64_t lda);
 
 /* Upload the resident RHS block R = [X | z] ([n][ld], nrhs <= 16 columns). */
 int gpmi_op_set_rhs(gpmi_op* op, const double* rhs, int64_t ld, int nrhs);
