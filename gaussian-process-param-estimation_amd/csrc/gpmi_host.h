@@ -1,6 +1,7 @@
 // Host-side helpers of the C-ABI translation units (gpmi_api.hip, gpmi_dense_*.hip,
-// gpmi_sparse_api.hip, gpmi_band_*.hip): the HIP error checks, the device guard and the
-// owners of device allocations, streams and events.
+// gpmi_sparse_api.hip, gpmi_sparse_assemble.hip, gpmi_sparse_spmm.hip,
+// gpmi_sparse_lanczos.hip, gpmi_sparse_cg.hip, gpmi_band_*.hip): the HIP error checks, the
+// device guard and the owners of device allocations, pinned host memory, streams and events.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -97,6 +98,26 @@ template <class T>
 struct DevBuf : DevMem {
   operator T*() const { return static_cast<T*>(p); }
   hipError_t reserve(size_t count) { return reserve_bytes(sizeof(T) * count); }
+};
+
+// Owner of one pinned host allocation (hipHostMalloc with `flags`).
+struct PinnedMem {
+  void* p = nullptr;
+  PinnedMem() = default;
+  PinnedMem(const PinnedMem&) = delete;
+  PinnedMem& operator=(const PinnedMem&) = delete;
+  ~PinnedMem() { (void)release(); }
+  hipError_t release() {
+    hipError_t e = p ? hipHostFree(p) : hipSuccess;
+    p = nullptr;
+    return e;
+  }
+  hipError_t alloc(size_t bytes, unsigned flags) {
+    hipError_t e = release();
+    if (e != hipSuccess) return e;
+    if ((e = hipHostMalloc(&p, bytes, flags)) != hipSuccess) p = nullptr;
+    return e;
+  }
 };
 
 // Owner of a stream or an event (created into h by the HIP call that fits).

@@ -150,7 +150,7 @@ __global__ void sample_reduce_kernel(const double* part, int jt, int D, double* 
 __global__ void cov_lowrank_kernel(const double* src, int64_t lds, double* dst, int64_t np,
                                    int64_t n, const double* U, int m);
 
-// Multi-shift CG Gram state (gpmi_sparse.hip, gpmi_sparse_api.hip); device pointers.
+// Multi-shift CG Gram state (gpmi_sparse.hip, gpmi_sparse_cg.hip); device pointers.
 #ifndef GPMI_LZ_JC
 #define GPMI_LZ_JC 16
 #endif

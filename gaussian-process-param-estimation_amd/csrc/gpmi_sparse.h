@@ -1,6 +1,7 @@
 // Kernels and constants of the sparse path shared by their definitions
 // (gpmi_sparse.hip; the CSR assembly in gpmi_matern.hip) and the host side that
-// launches them (gpmi_sparse_api.hip).
+// launches them (gpmi_sparse_assemble.hip, gpmi_sparse_spmm.hip, gpmi_sparse_lanczos.hip,
+// gpmi_sparse_cg.hip; the handle: gpmi_sp.h).
 #pragma once
 
 #include <hip/hip_runtime.h>
