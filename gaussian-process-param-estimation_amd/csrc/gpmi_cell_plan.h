@@ -3,6 +3,9 @@
 // coarsened while there are more cells than max(4 n, 1024). The points are counting-sorted
 // into cells, and the rows' locality order is the Morton order of the occupied cells.
 // Host check: tests/host/cell_plan_check.cpp.
+// A new point (the cross assembly of the sparse prediction) is not in the plan: its cell
+// comes from its coordinates (cross_cell_coord, cross_cell_range), compiled by the host and
+// by cross_cell_*_kernel alike. Host check: tests/host/cross_plan_check.cpp.
 #pragma once
 
 #include <algorithm>
@@ -11,7 +14,31 @@
 #include <utility>
 #include <vector>
 
+#if defined(__HIPCC__)
+#define GPMI_CELL_HD __host__ __device__
+#else
+#define GPMI_CELL_HD
+#endif
+
 namespace gpmi {
+
+// The unclamped cell coordinate floor((t - pmin) / wid) of a new point in one dimension,
+// limited to [-2, gdim + 1] before the integer conversion (so +-inf and huge coordinates
+// do not overflow; NaN gives -2). A training point p with |t - p| <= xcut |scale| < wid has
+// a cell coordinate (in [0, gdim - 1]) within 1 of it: the kept-pair guarantee of cell_plan.
+GPMI_CELL_HD inline int cross_cell_coord(double t, double pmin, double wid, int gdim) {
+  double x = std::floor((t - pmin) / wid);
+  if (!(x >= -2.0)) x = -2.0;
+  if (x > (double)gdim + 1.0) x = (double)gdim + 1.0;
+  return (int)x;
+}
+
+// The neighbour cells q - 1 .. q + 1 of that coordinate inside the grid: [*lo, *hi], empty
+// (*lo > *hi) for a point more than one cell outside the training box.
+GPMI_CELL_HD inline void cross_cell_range(int q, int gdim, int* lo, int* hi) {
+  *lo = q - 1 < 0 ? 0 : q - 1;
+  *hi = q + 1 > gdim - 1 ? gdim - 1 : q + 1;
+}
 
 struct CellPlan {
   double pmin[3], wid[3];      // the grid's origin and cell widths

@@ -17,6 +17,8 @@
 
 #include "gpmi_internal.h"
 #include "gpmi_matern_dev.h"
+#include "gpmi_sparse.h"      // CrossGrid
+#include "gpmi_cell_plan.h"   // cross_cell_coord, cross_cell_range
 
 #ifndef GPMI_MATERN_NT
 #define GPMI_MATERN_NT 1
@@ -470,6 +472,163 @@ __global__ __launch_bounds__(256) void csr_cell_fill_kernel(
     cnt += __popcll(m);
   });
   // one wave owns sj[w] / sv[w]: LDS order, fences keep the writes before the reads
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  const int64_t base = indptr[row];
+  for (int e = lane; e < cnt; e += 64) {
+    const int je = sj[w][e];
+    int rank = 0;
+    for (int f = 0; f < cnt; ++f) rank += sj[w][f] < je;
+    indices[base + rank] = je;
+    data[base + rank] = sv[w][e];
+  }
+}
+
+// ---------------------------------------------------------------------------
+// Cross assembly (the sparse prediction): the tapered correlations of nstar new
+// points with the n training points, K*[j][i] = matern(x_ji) if > tau, as a CSR
+// whose columns are device rows of K (the locality order; perm_dev[r] = original
+// point of device row r, inv its inverse; null: identity), ascending per row. The
+// same taper_keep as K's assembly, with the new point in the row's place: a new
+// point equal to training point i reproduces row i of K bit for bit. One wave per
+// new point, 4 per workgroup; no reference counterpart (it does not predict).
+// All pairs: the candidates in device order, so the ballot prefix already sorts.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void cross_count_kernel(
+    const double* __restrict__ points, int64_t n, const double* __restrict__ test, int64_t nstar,
+    int d, const double* __restrict__ scale, MaternParams P, double tau, double xcut,
+    int* __restrict__ row_nnz) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= nstar) return;
+  double pi[GPMI_MAX_DIM];
+#pragma unroll
+  for (int k = 0; k < GPMI_MAX_DIM; ++k) pi[k] = (k < d) ? test[row * d + k] : 0.0;
+  int cnt = 0;
+  for (int64_t j0 = 0; j0 < n; j0 += 64) {
+    const int64_t j = j0 + lane;
+    double v = 0.0;
+    const bool keep = (j < n) && taper_keep(pi, points, j, d, scale, P, tau, xcut, &v);
+    cnt += __popcll(__ballot(keep));
+  }
+  if (lane == 0) row_nnz[row] = cnt;
+}
+
+__global__ __launch_bounds__(256) void cross_fill_kernel(
+    const double* __restrict__ points, int64_t n, const double* __restrict__ test, int64_t nstar,
+    int d, const double* __restrict__ scale, MaternParams P, double tau, double xcut,
+    const int* __restrict__ perm_dev, const int64_t* __restrict__ indptr,
+    int* __restrict__ indices, double* __restrict__ data) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= nstar) return;
+  double pi[GPMI_MAX_DIM];
+#pragma unroll
+  for (int k = 0; k < GPMI_MAX_DIM; ++k) pi[k] = (k < d) ? test[row * d + k] : 0.0;
+  int64_t base = indptr[row];
+  const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  for (int64_t r0 = 0; r0 < n; r0 += 64) {
+    const int64_t r = r0 + lane;
+    double v = 0.0;
+    bool keep = false;
+    if (r < n) {
+      const int64_t j = perm_dev ? (int64_t)perm_dev[r] : r;
+      keep = taper_keep(pi, points, j, d, scale, P, tau, xcut, &v);
+    }
+    const unsigned long long m = __ballot(keep);
+    if (keep) {
+      const int64_t pos = base + __popcll(m & below);
+      indices[pos] = (int)r;
+      data[pos] = v;
+    }
+    base += __popcll(m);
+  }
+}
+
+// Cell list (d <= 3): the new point's neighbour cells from its coordinates
+// (gpmi_cell_plan.h: cross_cell_coord, cross_cell_range), dimension 0 fastest.
+template <typename F>
+__device__ __forceinline__ void for_each_cross_candidate(const double (&pi)[GPMI_MAX_DIM], int d,
+                                                         const CrossGrid& g,
+                                                         const int* __restrict__ cell_start,
+                                                         const int* __restrict__ perm, F&& f) {
+  const int lane = threadIdx.x & 63;
+  int lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+  bool any = true;
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    if (k < d) {
+      const int q = cross_cell_coord(pi[k], g.pmin[k], g.wid[k], g.gdim[k]);
+      cross_cell_range(q, g.gdim[k], &lo[k], &hi[k]);
+      any = any && lo[k] <= hi[k];
+    }
+  }
+  if (!any) return;   // wave-uniform: more than one cell outside the training box
+  for (int c2 = lo[2]; c2 <= hi[2]; ++c2)
+    for (int c1 = lo[1]; c1 <= hi[1]; ++c1)
+      for (int c0 = lo[0]; c0 <= hi[0]; ++c0) {
+        const int id = c0 + g.gdim[0] * (c1 + g.gdim[1] * c2);
+        const int b0 = cell_start[id], b1 = cell_start[id + 1];
+        for (int b = b0; b < b1; b += 64) {
+          const int k = b + lane;
+          f(k < b1 ? perm[k] : -1);
+        }
+      }
+}
+
+__global__ __launch_bounds__(256) void cross_cell_count_kernel(
+    const double* __restrict__ points, int64_t nstar, const double* __restrict__ test, int d,
+    const double* __restrict__ scale, MaternParams P, double tau, double xcut, CrossGrid g,
+    const int* __restrict__ cell_start, const int* __restrict__ perm, int* __restrict__ row_nnz) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= nstar) return;
+  double pi[GPMI_MAX_DIM];
+#pragma unroll
+  for (int k = 0; k < GPMI_MAX_DIM; ++k) pi[k] = (k < d) ? test[row * d + k] : 0.0;
+  int cnt = 0;
+  for_each_cross_candidate(pi, d, g, cell_start, perm, [&](int j) {
+    double v = 0.0;
+    const bool keep = (j >= 0) && taper_keep(pi, points, j, d, scale, P, tau, xcut, &v);
+    cnt += __popcll(__ballot(keep));
+  });
+  if (lane == 0) row_nnz[row] = cnt;
+}
+
+// The kept (device column, value) pairs of the row collected in LDS, written in
+// ascending column by rank as csr_cell_fill_kernel does (the host checked
+// max(row_nnz) <= CELL_CAP, from cross_cell_count_kernel's counts of the same pairs).
+__global__ __launch_bounds__(256) void cross_cell_fill_kernel(
+    const double* __restrict__ points, int64_t nstar, const double* __restrict__ test, int d,
+    const double* __restrict__ scale, MaternParams P, double tau, double xcut, CrossGrid g,
+    const int* __restrict__ cell_start, const int* __restrict__ perm,
+    const int* __restrict__ inv, const int64_t* __restrict__ indptr, int* __restrict__ indices,
+    double* __restrict__ data) {
+  __shared__ int sj[4][CELL_CAP];
+  __shared__ double sv[4][CELL_CAP];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+  const int64_t row = (int64_t)blockIdx.x * 4 + w;
+  if (row >= nstar) return;
+  double pi[GPMI_MAX_DIM];
+#pragma unroll
+  for (int k = 0; k < GPMI_MAX_DIM; ++k) pi[k] = (k < d) ? test[row * d + k] : 0.0;
+  const unsigned long long below = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+  int cnt = 0;
+  for_each_cross_candidate(pi, d, g, cell_start, perm, [&](int j) {
+    double v = 0.0;
+    const bool keep = (j >= 0) && taper_keep(pi, points, j, d, scale, P, tau, xcut, &v);
+    const unsigned long long m = __ballot(keep);
+    if (keep) {
+      const int pos = cnt + __popcll(m & below);
+      if (pos < CELL_CAP) {
+        sj[w][pos] = inv ? inv[j] : j;
+        sv[w][pos] = v;
+      }
+    }
+    cnt += __popcll(m);
+  });
+  if (cnt > CELL_CAP) cnt = CELL_CAP;   // (never: the host's check)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");

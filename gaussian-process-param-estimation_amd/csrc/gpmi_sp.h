@@ -9,6 +9,9 @@
 //                             (SpDense, SpWindow, SpTiming)
 //   gpmi_sparse_lanczos.hip   the three Lanczos forms (SpWork)
 //   gpmi_sparse_cg.hip        the blocked CG (SpWork) and the multi-shift CG (SpMs)
+//   gpmi_sparse_predict.hip   prediction on a sparse K: the cross CSR of new points and the
+//                             terms c, q, G (SpPredict; reads SpGeom, which
+//                             gpmi_sp_create_matern fills once)
 // Every device buffer is a DevBuf, every stream and event an owner (gpmi_host.h): streams
 // are declared before the buffers their work touches, gpmi_sp_destroy synchronises both.
 //
@@ -17,7 +20,8 @@
 // (work on ms.stream). The core, SpDense's K and a published SpWindow are read-only for
 // both; SpWork and dense.Yp belong to the main thread, SpMs and dense.Yp_ms to the ms
 // thread; SpTiming is shared under its mutex. Two threads in one role, or create / destroy
-// beside any call, are not supported.
+// beside any call, are not supported. The prediction (main thread: SpPredict, SpGeom) with
+// rhs == NULL reads ms.rhs_dev: set_rhs must not run beside it.
 #pragma once
 
 #include <atomic>
@@ -120,6 +124,38 @@ struct SpTiming {
   std::vector<SpmmRec> log;
 };
 
+// What gpmi_sp_create_matern keeps for a later cross assembly (gpmi_sparse_predict.hip):
+// about n (d + 2) words, read-only after create. Handles from a CSR or a dense K have
+// none (has = false): they take the cross matrix from the caller.
+struct SpGeom {
+  bool has = false;
+  int d = 0;
+  MaternParams P{};
+  double tau = 0.0, xcut = 0.0;
+  bool cells = false;          // the create found a plan: grid, cell_start, cell_perm
+  CrossGrid grid{};            // gdim, pmin, wid
+  DevBuf<double> points;       // [n][d], original order
+  DevBuf<double> scale;        // [scale | 1 / scale]
+  DevBuf<int> cell_start;      // [cells + 1]
+  DevBuf<int> cell_perm;       // [n] the points cell by cell
+  DevBuf<int> inv;             // [n] device row of each original point (perm's inverse)
+};
+
+// The sparse prediction (main thread): the last cross CSR (columns = device rows) and the
+// blocks that outlive a CG on work.ws.
+struct SpPredict {
+  int64_t nstar = 0, nnz = 0;
+  std::vector<int64_t> indptr_h;   // host copy of the row pointers
+  DevBuf<int64_t> indptr;
+  DevBuf<int> indices;
+  DevBuf<double> data;
+  DevBuf<double> test;         // [nstar][d] new points
+  DevBuf<int> cnt;             // [nstar] row counts
+  DevBuf<double> R, Sol;       // [n][s] R = [X z] in device order, S^-1 R
+  DevBuf<double> out;          // c [nstar][s], q [nstar], G [s][s]
+  DevBuf<double> partial;      // [NBLK][s][s] Gram partials
+};
+
 }  // namespace gpmi
 
 struct gpmi_sp {
@@ -144,6 +180,8 @@ struct gpmi_sp {
   gpmi::SpWindow win;
   gpmi::SpWork work;
   gpmi::SpTiming tim;
+  gpmi::SpGeom geom;
+  gpmi::SpPredict pred;
 };
 
 namespace gpmi {
@@ -172,6 +210,14 @@ int spmm(gpmi_sp* sp, const double* X, double* Y, int s, double eta, hipStream_t
 // out[j][c] = sum_i A_j[i][c] B[i][c], j < J  (device out)
 int col_dots(gpmi_sp* sp, const double* A, int64_t strideA, int J, const double* B, int s,
              double* out, double* partial = nullptr, hipStream_t st = nullptr);
+
+// gpmi_sparse_cg.hip
+// The blocked CG of gpmi_sp_cg on a block already on the device: work.ws holds
+// [X | R | P | Q], n * s doubles each, with the right-hand sides b in R (device row order).
+// Leaves the solutions in X. *it_used: iterations of the slowest column; *converged is
+// cleared when a column stopped at maxiter. Status 1: p^T (K + eta I) p <= 0.
+int cg_block_device(gpmi_sp* sp, double eta, int s, double rtol, int maxiter, int* it_used,
+                    bool* converged);
 
 inline unsigned grid_ns(int64_t n, int s) { return (unsigned)((n * s + 255) / 256); }
 

@@ -36,6 +36,26 @@ __global__ void csr_cell_fill_kernel(const double*, int64_t, int, const double*,
                                      const int*, const int64_t*, int*, double*);
 constexpr int CELL_CAP_HOST = 512;   // = CELL_CAP (gpmi_matern.hip)
 
+// Cross assembly of new points against the training points (gpmi_matern.hip): the cell
+// grid by value, the training points in original order, perm_dev / inv the locality
+// permutation and its inverse (null: identity), columns in device order
+struct CrossGrid {
+  double pmin[3], wid[3];
+  int gdim[3];   // 1 past d
+};
+__global__ void cross_count_kernel(const double*, int64_t, const double*, int64_t, int,
+                                   const double*, MaternParams, double, double, int*);
+__global__ void cross_fill_kernel(const double*, int64_t, const double*, int64_t, int,
+                                  const double*, MaternParams, double, double, const int*,
+                                  const int64_t*, int*, double*);
+__global__ void cross_cell_count_kernel(const double*, int64_t, const double*, int,
+                                        const double*, MaternParams, double, double, CrossGrid,
+                                        const int*, const int*, int*);
+__global__ void cross_cell_fill_kernel(const double*, int64_t, const double*, int,
+                                       const double*, MaternParams, double, double, CrossGrid,
+                                       const int*, const int*, const int*, const int64_t*, int*,
+                                       double*);
+
 // SpMM
 __global__ void csr_spmm_kernel(const int64_t*, const int*, const double*, int64_t, const double*,
                                 int64_t, double*, int64_t, int, int, double);
@@ -72,6 +92,15 @@ __global__ void cg_xr_kernel(const double*, const double*, double*, double*, con
 __global__ void cg_p_kernel(const double*, double*, const double*, const double*, const int*, int*,
                             const double*, int, int*, int64_t, int);
 __global__ void cg_init_kernel(const double*, double, int, double*, int*, int*, int*);
+
+// the sparse prediction's products with the cross CSR
+__global__ void cross_spmm_kernel(const int64_t*, const int*, const double*, int64_t,
+                                  const double*, int, double*);
+__global__ void cross_scatter_kernel(const int64_t*, const int*, const double*, int64_t, int,
+                                     double*);
+__global__ void cross_dot_kernel(const int64_t*, const int*, const double*, int64_t, int,
+                                 const double*, double*);
+__global__ void gram_partial_kernel(const double*, const double*, int64_t, int, double*);
 
 // Lanczos
 template <bool NT>

@@ -666,6 +666,84 @@ __global__ void cg_init_kernel(const double* __restrict__ rr, double rtol, int s
   act[c] = bn > rtol * bn;
 }
 
+// ---------------------------------------------------------------------------
+// The sparse prediction's products with the cross CSR K* [nstar][n] (columns =
+// device rows; gpmi_sparse_predict.hip). No reference counterpart.
+// ---------------------------------------------------------------------------
+
+// C[j][c] = sum_e K*[j][e] X[col_e][c], c < s <= 64: one wave per new point, lane =
+// (slot, c) with 64 / s slots taking the row's entries in turn, the slots summed in
+// ascending order (fixed). csr_spmm_kernel does not serve here: it reads X[row], and a
+// row of K* is no row of X.
+__global__ __launch_bounds__(256) void cross_spmm_kernel(const int64_t* __restrict__ indptr,
+                                                         const int* __restrict__ indices,
+                                                         const double* __restrict__ data,
+                                                         int64_t nstar,
+                                                         const double* __restrict__ X, int s,
+                                                         double* __restrict__ C) {
+  const int lane = threadIdx.x & 63;
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= nstar) return;
+  const int slots = 64 / s;
+  const int slot = lane / s, c = lane - slot * s;
+  const int64_t k0 = indptr[row], k1 = indptr[row + 1];
+  double acc = 0.0;
+  if (slot < slots)
+    for (int64_t e = k0 + slot; e < k1; e += slots) acc += data[e] * X[(int64_t)indices[e] * s + c];
+  double tot = 0.0;
+  for (int u = 0; u < slots; ++u) tot += __shfl(acc, (c + u * s) & 63);
+  if (slot == 0) C[row * s + c] = tot;
+}
+
+// B[col_e][c] = K*[j0 + c][e] for the s new points of a block (B [n][s] zeroed before):
+// the block's rows as right-hand sides. One wave per new point; every (col, c) is
+// written at most once (a row's columns are distinct), so there are no atomics.
+__global__ __launch_bounds__(256) void cross_scatter_kernel(const int64_t* __restrict__ indptr,
+                                                            const int* __restrict__ indices,
+                                                            const double* __restrict__ data,
+                                                            int64_t j0, int s,
+                                                            double* __restrict__ B) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= s) return;
+  const int64_t k0 = indptr[j0 + c], k1 = indptr[j0 + c + 1];
+  for (int64_t e = k0 + lane; e < k1; e += 64) B[(int64_t)indices[e] * s + c] = data[e];
+}
+
+// q[j0 + c] = sum_e K*[j0 + c][e] X[col_e][c]: one wave per new point, lane l takes
+// entries l, l + 64, ... in ascending order, then the xor butterfly (fixed order:
+// deterministic run to run).
+__global__ __launch_bounds__(256) void cross_dot_kernel(const int64_t* __restrict__ indptr,
+                                                        const int* __restrict__ indices,
+                                                        const double* __restrict__ data,
+                                                        int64_t j0, int s,
+                                                        const double* __restrict__ X,
+                                                        double* __restrict__ q) {
+  const int lane = threadIdx.x & 63;
+  const int c = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (c >= s) return;
+  const int64_t k0 = indptr[j0 + c], k1 = indptr[j0 + c + 1];
+  double acc = 0.0;
+  for (int64_t e = k0 + lane; e < k1; e += 64) acc += data[e] * X[(int64_t)indices[e] * s + c];
+  acc = wave_sum(acc);
+  if (lane == 0) q[j0 + c] = acc;
+}
+
+// partial[b][a][c] = sum over block b's rows of A[i][a] * B[i][c], a, c < s <= 32 (the
+// Gram R^T Sol; summed over b by col_dot_reduce_kernel with J = s). Thread t < s * s
+// owns (a, c); rows grid-strided, ascending.
+__global__ __launch_bounds__(1024) void gram_partial_kernel(const double* __restrict__ A,
+                                                            const double* __restrict__ B,
+                                                            int64_t n, int s,
+                                                            double* __restrict__ partial) {
+  const int t = threadIdx.x;
+  if (t >= s * s) return;
+  const int a = t / s, c = t - a * s;
+  double acc = 0.0;
+  for (int64_t i = blockIdx.x; i < n; i += gridDim.x) acc += A[i * s + a] * B[i * s + c];
+  partial[((int64_t)blockIdx.x * s + a) * s + c] = acc;
+}
+
 // Lanczos step k scalars on the device (no host round trip): alpha = the two
 // CGS2 passes' projections on V_k, beta = ||W||, a column whose beta falls below
 // 1e-13 max(1, |alpha|) is dead (invariant subspace: padding from then on).

@@ -60,8 +60,9 @@ int permute_csr(gpmi_sp* sp, std::vector<int>& lorder, const std::vector<int>& c
   for (int64_t r = 0; r < n; ++r) inv[lorder[r]] = (int)r;
   std::vector<int64_t> ip2(n + 1, 0);
   for (int64_t r = 0; r < n; ++r) ip2[r + 1] = ip2[r] + cnt[lorder[r]];
-  // (freed in reverse order: the old row starts, columns and values, then dpi)
-  DevBuf<int> dpi;
+  // (freed in reverse order: the old row starts, columns and values; the inverse stays
+  // with the handle for the cross assembly's device columns)
+  DevBuf<int>& dpi = sp->geom.inv;
   DevBuf<double> ddv2;
   DevBuf<int> dix2;
   DevBuf<int64_t> dip2;
@@ -104,8 +105,11 @@ extern "C" int gpmi_sp_create_matern(int device, const double* points, int64_t n
   double xcut = 0.0;
   if ((rc = taper_cutoff(sp.get(), P, tau, &xcut))) return rc;
   DevBuf<int> dcnt;
-  DevBuf<double> ds, dp;
-  DevBuf<int> dcell;   // [n] cell of each point, then gdim [d], cell_start, perm
+  // the points and [scale | 1 / scale] stay with the handle (SpGeom: a later cross
+  // assembly reads them), and with a plan its cell starts and cell order
+  SpGeom& geo = sp->geom;
+  DevBuf<double>&ds = geo.scale, &dp = geo.points;
+  DevBuf<int> dcell;   // [n] cell of each point, then gdim [d]
   HIP_TRY(dp.reserve(n * d));
   HIP_TRY(ds.reserve(2 * GPMI_MAX_DIM));   // [scale | 1 / scale]
   HIP_TRY(dcnt.reserve(n));
@@ -127,12 +131,15 @@ extern "C" int gpmi_sp_create_matern(int device, const double* points, int64_t n
     const char* ro = std::getenv("GPMI_SPARSE_REORDER");
     cells = cell_plan(points, n, d, scale, xcut, !(ro && std::atoi(ro) == 0), &plan);
   }
+  const bool planned = cells;
   if (cells) {
     const int64_t total = plan.total;
-    HIP_TRY(dcell.reserve(2 * n + d + total + 1));
+    HIP_TRY(dcell.reserve(n + d));
+    HIP_TRY(geo.cell_start.reserve(total + 1));
+    HIP_TRY(geo.cell_perm.reserve(n));
     dgdim = dcell + n;
-    dstart = dgdim + d;
-    dperm = dstart + total + 1;
+    dstart = geo.cell_start;
+    dperm = geo.cell_perm;
     HIP_TRY(hipMemcpyAsync(dcell, plan.cell.data(), sizeof(int) * n, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dgdim, plan.gdim.data(), sizeof(int) * d, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dstart, plan.start.data(), sizeof(int) * (total + 1),
@@ -171,6 +178,22 @@ extern "C" int gpmi_sp_create_matern(int device, const double* points, int64_t n
   HIP_TRY(hipStreamSynchronize(st));
   if (cells && (int64_t)plan.lorder.size() == n)
     if ((rc = permute_csr(sp.get(), plan.lorder, cnt))) return rc;
+  geo.d = d;
+  geo.P = P;
+  geo.tau = tau;
+  geo.xcut = xcut;
+  geo.cells = planned;
+  if (planned) {
+    for (int k = 0; k < 3; ++k) {
+      geo.grid.pmin[k] = k < d ? plan.pmin[k] : 0.0;
+      geo.grid.wid[k] = k < d ? plan.wid[k] : 1.0;
+      geo.grid.gdim[k] = k < d ? plan.gdim[k] : 1;
+    }
+  } else {
+    (void)geo.cell_start.release();
+    (void)geo.cell_perm.release();
+  }
+  geo.has = true;
   *out = sp.release();
   return 0;
 }

@@ -15,8 +15,85 @@
 
 using namespace gpmi;
 
+namespace gpmi {
+
+int cg_block_device(gpmi_sp* sp, double eta, int s, double rtol, int maxiter, int* it_used_out,
+                    bool* converged) {
+  const int64_t n = sp->n;
+  const int64_t ns = n * s;
+  double* X = sp->work.ws;
+  double* Rr = X + ns;
+  double* Pp = Rr + ns;
+  double* Q = Pp + ns;
+  // device scalars: pq, rr (double-buffered by iteration parity), thr = rtol ||b||,
+  // the active flags (double-buffered), the error flag and the iteration count
+  double* pq = sp->work.small;
+  double* rrb[2] = {sp->work.small + MAXS, sp->work.small + 2 * MAXS};
+  double* thr = sp->work.small + 3 * MAXS;
+  int* actb[2] = {reinterpret_cast<int*>(sp->work.small + 4 * MAXS),
+                  reinterpret_cast<int*>(sp->work.small + 5 * MAXS)};
+  int* err = reinterpret_cast<int*>(sp->work.small + 6 * MAXS);
+  int* iters = err + 1;
+  HIP_TRY(hipMemcpyAsync(Pp, Rr, sizeof(double) * ns, hipMemcpyDeviceToDevice, sp->stream));
+  HIP_TRY(hipMemsetAsync(X, 0, sizeof(double) * ns, sp->stream));
+  if (int rc = col_dots(sp, Rr, 0, 1, Rr, s, rrb[0])) return rc;
+  hipLaunchKernelGGL(cg_init_kernel, dim3(1), dim3(64), 0, sp->stream, rrb[0], rtol, s, thr,
+                     actb[0], err, iters);
+  LAUNCH_CHECK("cg_init_kernel");
+  // The host reads the flags every CG_POLL iterations (one round trip each, not two per
+  // iteration): iterations queued after the last column stopped do no vector work.
+  constexpr int CG_POLL = 8;
+  std::vector<int> flags(MAXS + 2);
+  const unsigned grid = grid_ns(n, s);
+  for (int it = 0; it < maxiter; ++it) {
+    const int cur = it & 1;
+    if (int rc = spmm(sp, Pp, Q, s, eta)) return rc;
+    if (int rc = col_dots(sp, Pp, 0, 1, Q, s, pq)) return rc;
+    hipLaunchKernelGGL(cg_xr_kernel, dim3(grid), dim3(256), 0, sp->stream, Pp, Q, X, Rr,
+                       rrb[cur], pq, actb[cur], n, s, err);   // x += a p, r -= a q
+    LAUNCH_CHECK("cg_xr_kernel");
+    if (int rc = col_dots(sp, Rr, 0, 1, Rr, s, rrb[cur ^ 1])) return rc;
+    hipLaunchKernelGGL(cg_p_kernel, dim3(grid), dim3(256), 0, sp->stream, Rr, Pp, rrb[cur],
+                       rrb[cur ^ 1], actb[cur], actb[cur ^ 1], thr, it, iters, n, s);
+    LAUNCH_CHECK("cg_p_kernel");   // p = r + b p
+    if ((it + 1) % CG_POLL == 0 || it + 1 == maxiter) {
+      HIP_TRY(hipMemcpyAsync(flags.data(), actb[cur ^ 1], sizeof(int) * s, hipMemcpyDeviceToHost,
+                            sp->stream));
+      HIP_TRY(hipMemcpyAsync(flags.data() + MAXS, err, sizeof(int), hipMemcpyDeviceToHost,
+                            sp->stream));
+      HIP_TRY(hipStreamSynchronize(sp->stream));
+      if (flags[MAXS])
+        return set_error(1, "CG: p^T (K + eta I) p <= 0 (K + eta I is not positive definite)");
+      bool any = false;
+      for (int c = 0; c < s; ++c) any = any || flags[c];
+      if (!any) break;
+    }
+  }
+  // the residual norms after the last iteration that ran sit in rrb[it_used & 1] (rrb[0]
+  // when none ran); the no-op iterations queued after it rewrite the same values
+  std::vector<double> rr(s), bnt(s);
+  HIP_TRY(hipMemcpyAsync(flags.data() + MAXS, err, sizeof(int) * 2, hipMemcpyDeviceToHost,
+                        sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  if (flags[MAXS])
+    return set_error(1, "CG: p^T (K + eta I) p <= 0 (K + eta I is not positive definite)");
+  const int it_used = flags[MAXS + 1];
+  *it_used_out = it_used;
+  HIP_TRY(hipMemcpyAsync(bnt.data(), thr, sizeof(double) * s, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipMemcpyAsync(rr.data(), rrb[it_used & 1], sizeof(double) * s, hipMemcpyDeviceToHost,
+                        sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  for (int c = 0; c < s; ++c)
+    if (!(std::sqrt(rr[c]) <= bnt[c])) *converged = false;
+  return 0;
+}
+
+}  // namespace gpmi
+
 extern "C" {
 
+// Upload a block of at most MAXS columns (permuted into the device row order), the CG on
+// the device (cg_block_device), download.
 int gpmi_sp_cg(gpmi_sp* sp, double eta, const double* rhs, int64_t ld, int nrhs, double rtol,
                int maxiter, double* sol, int64_t ldsol, int* iterations) {
   if (!sp) return set_error(-1006, "null handle");
@@ -31,72 +108,13 @@ int gpmi_sp_cg(gpmi_sp* sp, double eta, const double* rhs, int64_t ld, int nrhs,
     HIP_TRY(sp->work.ws.reserve((size_t)4 * ns));
     double* X = sp->work.ws;
     double* Rr = X + ns;
-    double* Pp = Rr + ns;
-    double* Q = Pp + ns;
-    // device scalars: pq, rr (double-buffered by iteration parity), thr = rtol ||b||,
-    // the active flags (double-buffered), the error flag and the iteration count
-    double* pq = sp->work.small;
-    double* rrb[2] = {sp->work.small + MAXS, sp->work.small + 2 * MAXS};
-    double* thr = sp->work.small + 3 * MAXS;
-    int* actb[2] = {reinterpret_cast<int*>(sp->work.small + 4 * MAXS),
-                    reinterpret_cast<int*>(sp->work.small + 5 * MAXS)};
-    int* err = reinterpret_cast<int*>(sp->work.small + 6 * MAXS);
-    int* iters = err + 1;
     std::vector<double> h((size_t)ns);
     for (int64_t i = 0; i < n; ++i)
       for (int c = 0; c < s; ++c) h[(size_t)i * s + c] = rhs[orig_row(sp, i) * ld + c0 + c];
     HIP_TRY(hipMemcpyAsync(Rr, h.data(), sizeof(double) * ns, hipMemcpyHostToDevice, sp->stream));
-    HIP_TRY(hipMemcpyAsync(Pp, Rr, sizeof(double) * ns, hipMemcpyDeviceToDevice, sp->stream));
-    HIP_TRY(hipMemsetAsync(X, 0, sizeof(double) * ns, sp->stream));
-    if (int rc = col_dots(sp, Rr, 0, 1, Rr, s, rrb[0])) return rc;
-    hipLaunchKernelGGL(cg_init_kernel, dim3(1), dim3(64), 0, sp->stream, rrb[0], rtol, s, thr,
-                       actb[0], err, iters);
-    LAUNCH_CHECK("cg_init_kernel");
-    // The host reads the flags every CG_POLL iterations (one round trip each, not two per
-    // iteration): iterations queued after the last column stopped do no vector work.
-    constexpr int CG_POLL = 8;
-    std::vector<int> flags(MAXS + 2);
-    const unsigned grid = grid_ns(n, s);
-    for (int it = 0; it < maxiter; ++it) {
-      const int cur = it & 1;
-      if (int rc = spmm(sp, Pp, Q, s, eta)) return rc;
-      if (int rc = col_dots(sp, Pp, 0, 1, Q, s, pq)) return rc;
-      hipLaunchKernelGGL(cg_xr_kernel, dim3(grid), dim3(256), 0, sp->stream, Pp, Q, X, Rr,
-                         rrb[cur], pq, actb[cur], n, s, err);   // x += a p, r -= a q
-      LAUNCH_CHECK("cg_xr_kernel");
-      if (int rc = col_dots(sp, Rr, 0, 1, Rr, s, rrb[cur ^ 1])) return rc;
-      hipLaunchKernelGGL(cg_p_kernel, dim3(grid), dim3(256), 0, sp->stream, Rr, Pp, rrb[cur],
-                         rrb[cur ^ 1], actb[cur], actb[cur ^ 1], thr, it, iters, n, s);
-      LAUNCH_CHECK("cg_p_kernel");   // p = r + b p
-      if ((it + 1) % CG_POLL == 0 || it + 1 == maxiter) {
-        HIP_TRY(hipMemcpyAsync(flags.data(), actb[cur ^ 1], sizeof(int) * s, hipMemcpyDeviceToHost,
-                              sp->stream));
-        HIP_TRY(hipMemcpyAsync(flags.data() + MAXS, err, sizeof(int), hipMemcpyDeviceToHost,
-                              sp->stream));
-        HIP_TRY(hipStreamSynchronize(sp->stream));
-        if (flags[MAXS])
-          return set_error(1, "CG: p^T (K + eta I) p <= 0 (K + eta I is not positive definite)");
-        bool any = false;
-        for (int c = 0; c < s; ++c) any = any || flags[c];
-        if (!any) break;
-      }
-    }
-    // the residual norms after the last iteration that ran sit in rrb[it_used & 1] (rrb[0]
-    // when none ran); the no-op iterations queued after it rewrite the same values
-    std::vector<double> rr(s), bnt(s);
-    HIP_TRY(hipMemcpyAsync(flags.data() + MAXS, err, sizeof(int) * 2, hipMemcpyDeviceToHost,
-                          sp->stream));
-    HIP_TRY(hipStreamSynchronize(sp->stream));
-    if (flags[MAXS])
-      return set_error(1, "CG: p^T (K + eta I) p <= 0 (K + eta I is not positive definite)");
-    const int it_used = flags[MAXS + 1];
+    int it_used = 0;
+    if (int rc = cg_block_device(sp, eta, s, rtol, maxiter, &it_used, &converged)) return rc;
     max_it_used = std::max(max_it_used, it_used);
-    HIP_TRY(hipMemcpyAsync(bnt.data(), thr, sizeof(double) * s, hipMemcpyDeviceToHost, sp->stream));
-    HIP_TRY(hipMemcpyAsync(rr.data(), rrb[it_used & 1], sizeof(double) * s, hipMemcpyDeviceToHost,
-                          sp->stream));
-    HIP_TRY(hipStreamSynchronize(sp->stream));
-    for (int c = 0; c < s; ++c)
-      if (!(std::sqrt(rr[c]) <= bnt[c])) converged = false;
     HIP_TRY(hipMemcpyAsync(h.data(), X, sizeof(double) * ns, hipMemcpyDeviceToHost, sp->stream));
     HIP_TRY(hipStreamSynchronize(sp->stream));
     for (int64_t i = 0; i < n; ++i)

@@ -155,6 +155,18 @@ SIGNATURES = {
     'gpmi_sp_spmm_info': (ctypes.c_int, [c_op_p, c_int_p, c_double_p, c_int_p]),
     'gpmi_sp_spmm_kernel': (ctypes.c_int, [c_op_p, ctypes.c_int, c_int_p]),
     'gpmi_band_last_timing': (ctypes.c_int, [c_op_p, c_double_p, c_double_p, c_double_p]),
+    'gpmi_sp_predict_terms': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p, c_i64,
+                                             ctypes.c_int, c_double_p, c_i64, ctypes.c_int,
+                                             ctypes.c_int, ctypes.c_double, ctypes.c_int,
+                                             c_double_p, c_double_p, c_double_p, c_int_p]),
+    'gpmi_sp_predict_terms_csr': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p, c_i64,
+                                                 ctypes.c_int, c_i64, ctypes.POINTER(c_i64),
+                                                 c_int_p, c_double_p, ctypes.c_int,
+                                                 ctypes.c_double, ctypes.c_int, c_double_p,
+                                                 c_double_p, c_double_p, c_int_p]),
+    'gpmi_sp_cross_matern': (ctypes.c_int, [c_op_p, c_double_p, c_i64, ctypes.c_int,
+                                            ctypes.POINTER(c_i64)]),
+    'gpmi_sp_get_cross': (ctypes.c_int, [c_op_p, ctypes.POINTER(c_i64), c_int_p, c_double_p]),
 }
 
 
@@ -898,7 +910,9 @@ class SparseOperator(object):
         check(lib.gpmi_sp_create_matern(device, dptr(points), points.shape[0], points.shape[1],
                                         dptr(scale), float(nu), float(tau), ctypes.byref(h)),
               'gpmi_sp_create_matern')
-        return cls(h, device)
+        out = cls(h, device)
+        out.dim = points.shape[1]   # (the handle keeps the geometry: cross, predict_terms)
+        return out
 
     @classmethod
     def from_csr(cls, K, device=None):
@@ -1098,6 +1112,102 @@ class SparseOperator(object):
         check(self.lib.gpmi_sp_msgram_segments(self.h, cap, w, k, ctypes.byref(m)),
               'gpmi_sp_msgram_segments')
         return [(w[q], k[q]) for q in range(m.value)]
+
+    dim = 0   # point dimension of a handle with geometry (from_points); 0: none
+
+    def cross(self, test_points):
+        """The tapered cross-correlation K* of ``test_points`` (n* x d) with the
+        training points as a ``scipy.sparse.csr_matrix`` (n*, n): entry [j, i] =
+        matern(x_ji) where it exceeds the operator's tau (gpmi_sp_cross_matern,
+        gpmi_sp_get_cross), assembled on the device by K's own kernel arithmetic.
+        Needs an operator from ``from_points`` (ValueError otherwise)."""
+        import scipy.sparse
+        if not self.dim:
+            raise ValueError('cross: the operator keeps no geometry (not from from_points)')
+        tp = as_c(test_points)
+        if tp.ndim != 2 or tp.shape[1] != self.dim or tp.shape[0] < 1:
+            raise ValueError('test_points must be n* x %d with n* >= 1' % self.dim)
+        nnz = c_i64()
+        check(self.lib.gpmi_sp_cross_matern(self.h, dptr(tp), tp.shape[0], tp.shape[1],
+                                            ctypes.byref(nnz)), 'gpmi_sp_cross_matern')
+        ip = numpy.empty(tp.shape[0] + 1, dtype=numpy.int64)
+        ix = numpy.empty(nnz.value, dtype=numpy.int32)
+        dv = numpy.empty(nnz.value)
+        check(self.lib.gpmi_sp_get_cross(self.h, ip.ctypes.data_as(ctypes.POINTER(c_i64)),
+                                         ix.ctypes.data_as(c_int_p), dptr(dv)),
+              'gpmi_sp_get_cross')
+        return scipy.sparse.csr_matrix((dv, ix, ip), shape=(tp.shape[0], self.n))
+
+    def predict_terms(self, eta, R, test_points=None, cross=None, want_q=True, rtol=1e-6,
+                      maxiter=None):
+        """The prediction terms on a sparse K (gpmi_sp_predict_terms): with
+        S = K + eta I and R [n, s] (s <= 32; None: the block of set_rhs),
+          c[n*, s] = K* S^-1 R,  q[n*] = diag(K* S^-1 K*^T),  G[s, s] = R^T S^-1 R,
+        K* the tapered cross-correlation of ``test_points`` (n* x d) assembled on
+        the device (an operator from ``from_points``), or ``cross``, an (n*, n) scipy
+        sparse matrix or ndarray (any operator; gpmi_sp_predict_terms_csr). One CG
+        for S^-1 R, one product for c and, with ``want_q``, one CG per block of
+        32 rows of K*, all on the device. Returns (c, q, G), q None without
+        ``want_q``; the iteration counts (R solve, most of a variance block) are
+        left in ``last_predict_iterations``. Warns (RuntimeWarning) when a CG
+        stopped at maxiter; raises numpy.linalg.LinAlgError when S is not positive
+        definite."""
+        if R is None:
+            if not self.rhs_cols:
+                raise ValueError('predict_terms: no resident right-hand sides (set_rhs)')
+            R2, s, ld = None, self.rhs_cols, self.rhs_cols
+        else:
+            R = as_c(R)
+            R2 = R[:, None] if R.ndim == 1 else R
+            if R2.shape[0] != self.n:
+                raise ValueError('predict_terms: R has %d rows, the operator %d'
+                                 % (R2.shape[0], self.n))
+            s = ld = R2.shape[1]
+        if not 1 <= s <= 32:
+            raise ValueError('predict_terms: R must have 1 to 32 columns')
+        maxiter = 10 * self.n if maxiter is None else int(maxiter)
+        it = (ctypes.c_int * 2)()
+        rp = None if R2 is None else dptr(R2)
+        if cross is not None:
+            import scipy.sparse
+            # (a copy: the caller's matrix is not sorted in place)
+            Ks = cross.tocsr().copy() if scipy.sparse.issparse(cross) else \
+                scipy.sparse.csr_matrix(numpy.atleast_2d(numpy.asarray(cross, dtype=float)))
+            if Ks.shape[1] != self.n or Ks.shape[0] < 1:
+                raise ValueError('cross must be n* x %d with n* >= 1' % self.n)
+            Ks.sum_duplicates()
+            Ks.sort_indices()
+            nstar = Ks.shape[0]
+            ip = numpy.ascontiguousarray(Ks.indptr, dtype=numpy.int64)
+            ix = numpy.ascontiguousarray(Ks.indices, dtype=numpy.int32)
+            dv = as_c(Ks.data)
+        else:
+            if test_points is None:
+                raise ValueError('predict_terms needs test_points or cross')
+            if not self.dim:
+                raise ValueError('predict_terms: the operator keeps no geometry (not from '
+                                 'from_points): pass cross, the n* x n cross-correlation')
+            tp = as_c(test_points)
+            if tp.ndim != 2 or tp.shape[1] != self.dim or tp.shape[0] < 1:
+                raise ValueError('test_points must be n* x %d with n* >= 1' % self.dim)
+            nstar = tp.shape[0]
+        c = numpy.empty((nstar, s))
+        q = numpy.empty(nstar) if want_q else None
+        G = numpy.empty((s, s))
+        qp = dptr(q) if want_q else None
+        if cross is not None:
+            rc = self.lib.gpmi_sp_predict_terms_csr(
+                self.h, float(eta), rp, ld, s, nstar, ip.ctypes.data_as(ctypes.POINTER(c_i64)),
+                ix.ctypes.data_as(c_int_p), dptr(dv), int(bool(want_q)), float(rtol), maxiter,
+                dptr(c), qp, dptr(G), it)
+        else:
+            rc = self.lib.gpmi_sp_predict_terms(
+                self.h, float(eta), rp, ld, s, dptr(tp), nstar, tp.shape[1], int(bool(want_q)),
+                float(rtol), maxiter, dptr(c), qp, dptr(G), it)
+        check(rc, 'gpmi_sp_predict_terms')
+        self.last_predict_iterations = (it[0], it[1])
+        self._warn_unconverged('predict_terms', maxiter)
+        return c, q, G
 
     def _warn_unconverged(self, what, maxiter):
         """scipy's cg (the reference's sparse solve, _linear_solver.py:64,68)

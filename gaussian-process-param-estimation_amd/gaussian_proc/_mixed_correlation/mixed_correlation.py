@@ -31,7 +31,9 @@ once per operator.
   the probes' standard error).
 * sparse K: 'slq' (logdet / traceinv by device Lanczos quadrature) and
   'hutchinson' traceinv (CG solves); solve by device CG as the reference's
-  linear_solver (_linear_solver.py:57-68). The exact methods ('cholesky', and
+  linear_solver (_linear_solver.py:57-68); predict_terms by CGs whose right-hand
+  sides stay on the device (mean and variance; the joint covariance, sampling,
+  leave-one-out and the scale gradient are not built on a sparse K). The exact methods ('cholesky', and
   'hutchinson' logdet, which the reference hands to imate's sparse Cholesky
   via CHOLMOD, :250-261; 'eigenvalue', whose eigh of a sparse K raises in the
   reference, :76-79) run the dense device paths above on a copy of K scattered
@@ -110,6 +112,13 @@ def _check_options(method, options):
     if bad:
         raise TypeError("imate_options for imate_method='%s': unexpected keyword argument%s %s"
                         % (method, 's' if len(bad) > 1 else '', ', '.join(map(repr, bad))))
+
+
+class _CrossRequired(ValueError, NotImplementedError):
+    """predict_terms on a scipy-CSR K without ``cross``: an argument is missing
+    (ValueError), and assembling k* for a K that carries no kernel parameters stays
+    unimplemented (NotImplementedError, what this call raised before prediction on a
+    sparse K existed)."""
 
 
 class MixedCorrelation(object):
@@ -706,7 +715,7 @@ class MixedCorrelation(object):
         return self._exact_terms(etas)
 
     def predict_terms(self, eta, X, z, test_points=None, cross=None, points=None,
-                      correlation_scale=None, nu=None):
+                      correlation_scale=None, nu=None, return_q=True):
         """The device terms of a prediction at n* new points (the reference has no
         counterpart; it stops at training). With S = K + eta I and R = [X z]:
           c[n*, m + 1] = (R^T S^-1 k*_j)_j,   q[n*] = (k*_j^T S^-1 k*_j)_j,
@@ -718,14 +727,48 @@ class MixedCorrelation(object):
         ``test_points`` (n* x d) and the kernel parameters, which default to those
         of a DeviceCorrelation K and are required (``points``,
         ``correlation_scale``, ``nu``) for an ndarray K; or it is the host matrix
-        ``cross`` (n* x n), for a K that is not this package's Matérn. A sparse K
-        raises NotImplementedError; K + eta I not positive definite raises
+        ``cross`` (n* x n), for a K that is not this package's Matérn.
+        On a sparse K the model is the tapered kernel (matern(x) where it exceeds
+        tau, else 0), so k* is tapered too and sparse: it is assembled on the device
+        from the geometry a DeviceSparseCorrelation K keeps, or it is ``cross``, an
+        (n*, n) scipy sparse matrix or ndarray, which a scipy-CSR K requires
+        (ValueError without). The terms then come from conjugate gradients with
+        ``cg_rtol`` whose right-hand sides and solutions stay on the device
+        (_hip.SparseOperator.predict_terms, csrc/gpmi_sparse_predict.hip): one for
+        S^-1 R, and for q one per block of 32 new points; ``return_q=False`` skips
+        those and returns q = None (on a dense K q costs nothing more: it is
+        computed and dropped). K + eta I not positive definite raises
         numpy.linalg.LinAlgError. Returns (c, q, G)."""
+        if self.sparse:
+            return self._sparse_predict_terms(eta, X, z, test_points, cross, return_q)
         test_points, points, correlation_scale, nu = self._predict_args(
             X, test_points, cross, points, correlation_scale, nu, 'predict_terms')
         self.set_rhs(X, z)
-        return self.op.predict_terms(eta, test_points=test_points, points=points,
-                                     scale=correlation_scale, nu=nu, cross=cross)
+        c, q, G = self.op.predict_terms(eta, test_points=test_points, points=points,
+                                        scale=correlation_scale, nu=nu, cross=cross)
+        return c, (q if return_q else None), G
+
+    def _sparse_predict_terms(self, eta, X, z, test_points, cross, return_q):
+        X = numpy.asarray(X, dtype=float)
+        if X.ndim != 2 or X.shape[0] != self.n:
+            raise ValueError('X must be %d x m' % self.n)
+        R = numpy.column_stack([X, numpy.asarray(z, dtype=float)])
+        if cross is None:
+            if not isinstance(self.K, DeviceSparseCorrelation):
+                raise _CrossRequired('a scipy sparse K needs cross, the (n*, n) tapered '
+                                     'cross-correlation of the new points (generate_cross_'
+                                     'correlation(test_points, K) of a DeviceSparseCorrelation K '
+                                     'gives it)')
+            if test_points is None:
+                raise ValueError('predict_terms needs test_points or cross')
+            test_points = numpy.ascontiguousarray(test_points, dtype=float)
+            d = self.K.points.shape[1]
+            if test_points.ndim != 2 or test_points.shape[1] != d:
+                raise ValueError('test_points must be n* x %d' % d)
+            return self.sop.predict_terms(eta, R, test_points=test_points,
+                                          want_q=bool(return_q), rtol=self.cg_rtol)
+        return self.sop.predict_terms(eta, R, cross=cross, want_q=bool(return_q),
+                                      rtol=self.cg_rtol)
 
     def predict_cov_terms(self, eta, X, z, test_points=None, cross=None, cross_star=None,
                           points=None, correlation_scale=None, nu=None):
@@ -880,7 +923,8 @@ class MixedCorrelation(object):
         """The checks and kernel-parameter defaults predict_terms and
         predict_cov_terms share -> (test_points, points, correlation_scale, nu)."""
         if self.sparse:
-            raise NotImplementedError('prediction on a sparse K is not implemented')
+            raise NotImplementedError('%s on a sparse K is not implemented (predict_terms is: '
+                                      'the mean and the variance)' % who)
         X = numpy.asarray(X, dtype=float)
         if X.ndim != 2 or X.shape[0] != self.n:
             raise ValueError('X must be %d x m' % self.n)

@@ -203,8 +203,12 @@ class GaussianProcess(object):
             mean, _ = _predict_from_terms(c, q, G, X_star, sigma, sigma0, noise=noise)
             return mean, _predict_cov_from_terms(c, G, C0, X_star, sigma, sigma0, noise=noise)
         kernel_params.pop('cross_star', None)   # (only the covariance reads it)
+        # (on a sparse K q costs a CG per block of new points: not asked for the mean alone)
         c, q, G = self.likelihood.K_mixed.predict_terms(eta, X, z, test_points=test_points,
+                                                        return_q=bool(return_var),
                                                         **kernel_params)
+        if q is None:
+            q = numpy.zeros(c.shape[0])   # (the mean does not read q)
         mean, var = _predict_from_terms(c, q, G, X_star, sigma, sigma0, noise=noise)
         return (mean, var) if return_var else mean
 

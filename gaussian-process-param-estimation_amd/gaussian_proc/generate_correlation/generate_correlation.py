@@ -127,7 +127,21 @@ def generate_cross_correlation(test_points, points, correlation_scale=0.1, nu=0.
     ``numpy.ndarray`` (n*, n), entry [j, i] the correlation of test point j with
     point i, from the same device arithmetic as ``generate_correlation`` (a test
     point equal to a training point reproduces that matrix's entry bit for bit).
-    The reference has no counterpart (it does not predict)."""
+    The reference has no counterpart (it does not predict).
+
+    With a :class:`DeviceSparseCorrelation` K in place of ``points`` the result is
+    the tapered cross-correlation as a ``scipy.sparse.csr_matrix`` (n*, n): the
+    entries above K's threshold tau, from K's own points, scale and nu
+    (``correlation_scale`` and ``nu`` are then ignored), assembled on K's device;
+    a test point equal to training point i reproduces row i of ``K.tocsr()``."""
+    if isinstance(points, DeviceSparseCorrelation):
+        test_points = numpy.ascontiguousarray(test_points, dtype=float)
+        if test_points.ndim != 2:
+            raise ValueError('test_points must be a 2D array (num_points, dimension)')
+        if test_points.shape[1] != points.points.shape[1]:
+            raise ValueError('test_points have dimension %d, points %d'
+                             % (test_points.shape[1], points.points.shape[1]))
+        return points.op.cross(test_points)
     points = numpy.ascontiguousarray(points, dtype=float)
     test_points = numpy.ascontiguousarray(test_points, dtype=float)
     if points.ndim != 2 or test_points.ndim != 2:

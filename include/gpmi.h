@@ -448,6 +448,53 @@ int gpmi_sp_set_timing(gpmi_sp* sp, int enable);
 int gpmi_sp_spmm_timing(gpmi_sp* sp, int max_widths, int* n_widths, int* widths,
                         int* launches, double* total_ms);
 
+/* ------------------------------------------------- prediction on a sparse K --
+ * The model on a sparse K is the tapered kernel k_tau(x) = matern(x) if matern(x) > tau,
+ * else 0, so k*_j, the correlations of new point j with the training points, follows the
+ * same rule: K* [nstar][n] is sparse. With S = K + eta I and R = [X z] (nrhs <= 32
+ * columns):
+ *   c[nstar][nrhs] = K* S^-1 R,   q[nstar] = diag(K* S^-1 K*^T),   G[nrhs][nrhs] = R^T S^-1 R,
+ * the terms gpmi_op_predict_terms returns from a dense factor. Here: one blocked CG for
+ * S^-1 R, one gather product for c, and for q one CG per block of <= 32 rows of K*
+ * (GPMI_SP_PREDICT_S, default 32) scattered into a device block; right-hand sides and
+ * solutions never leave the device. The CGs stop per column at ||r|| <= rtol ||b|| or at
+ * maxiter (gpmi_sp_last_status then reports 0); p^T S p <= 0 returns 1. Empty rows of K*
+ * are legal and give c = 0 and q = 0 exactly.
+ * No reference counterpart (the reference stops at training). */
+
+/* c, q (when want_q; else q may be NULL and is not touched) and G for the nstar new points
+ * test_points [nstar][d], K* assembled on the device from the geometry
+ * gpmi_sp_create_matern kept (same kernel arithmetic: a new point equal to training point
+ * i reproduces row i of K bit for bit). -1108: the handle has no geometry (from a CSR or
+ * a dense K), or d is not its dimension. rhs [n][ld], original row order; rhs == NULL:
+ * the block of gpmi_sp_set_rhs (nrhs equal to its width). iterations[2] = {the R solve,
+ * the most of any variance block}. -1104: nrhs outside [1, 32], maxiter < 0, rtol negative
+ * or NaN. No reference counterpart. */
+int gpmi_sp_predict_terms(gpmi_sp* sp, double eta, const double* rhs, int64_t ld, int nrhs,
+                          const double* test_points, int64_t nstar, int d, int want_q,
+                          double rtol, int maxiter, double* c, double* q, double* G,
+                          int* iterations);
+/* The same with the caller's K*: a host CSR [nstar][n] over original column indices
+ * (indptr int64, indices int32 strictly ascending per row, data fp64), for any handle.
+ * It is permuted to the device's row order and re-sorted per row at upload. -1109:
+ * row pointers not ascending, a column outside [0, n) or a row's columns not strictly
+ * ascending. No reference counterpart. */
+int gpmi_sp_predict_terms_csr(gpmi_sp* sp, double eta, const double* rhs, int64_t ld, int nrhs,
+                              int64_t nstar, const int64_t* indptr, const int* indices,
+                              const double* data, int want_q, double rtol, int maxiter,
+                              double* c, double* q, double* G, int* iterations);
+/* Assemble K* of test_points [nstar][d] only (kept on the device until the next cross
+ * assembly or prediction on this handle); *nnz its entries. The cell list of the create
+ * when it found a plan; all pairs for d > 3, under GPMI_SPARSE_BRUTE=1 (read at this
+ * call) or when a row holds more than 512 kept entries: the CSR is identical either way.
+ * -1108 as above. No reference counterpart. */
+int gpmi_sp_cross_matern(gpmi_sp* sp, const double* test_points, int64_t nstar, int d,
+                         int64_t* nnz);
+/* The last cross CSR (assembled or given) back on the host: indptr[nstar + 1], and
+ * indices / data of *nnz entries, original column indices ascending per row. -1110: there
+ * is none. No reference counterpart. */
+int gpmi_sp_get_cross(gpmi_sp* sp, int64_t* indptr, int* indices, double* data);
+
 /* -------------------------------------------------------------------- band --
  * One-time orthogonal reduction of an operator's K to symmetric band form,
  * K = Q B Q^T with bandwidth 128 (blocked Householder panels, two-sided
