@@ -197,6 +197,7 @@ int gpmi_band_set_rhs(gpmi_band* b, const double* rhs, int64_t ld, int nrhs) {
   DeviceGuard g(b->device);
   hipStream_t s = b->stream;
   const std::vector<double> h = pack_rhs(b, rhs, ld, nrhs);
+  b->eval.sol_path = 0;   // a solution read back would belong to the old RHS
   HIP_TRY(hipEventRecord(b->ev0, s));
   HIP_TRY(hipMemcpyAsync(b->Y, h.data(), sizeof(double) * h.size(), hipMemcpyHostToDevice, s));
   for (int j = 0; j + 1 < b->nt; ++j) {
@@ -225,6 +226,126 @@ int gpmi_band_get(gpmi_band* b, double* B_out, int64_t ld) {
       const int64_t hi = std::max(i, j), lo = std::min(i, j);
       B_out[i * ld + j] = (hi - lo <= TS) ? h[(size_t)hi * np + lo] : 0.0;
     }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Read-backs of what the stages left on the device (tests and diagnostics): each is
+// a copy on the handle's stream and a rearrangement on the host; none launches a
+// kernel or changes what a later call computes.
+// ---------------------------------------------------------------------------
+
+int gpmi_band_get_reduction(gpmi_band* b, double* B_out, double* V_out, double* T_out,
+                            int64_t ld) {
+  if (!b) return set_error(-1006, "null handle");
+  if (!B_out || !V_out || !T_out) return set_error(-1004, "null output");
+  if (ld < b->n_pad) return set_error(-1003, "ld < n_pad");
+  DeviceGuard g(b->device);
+  const int64_t np = b->n_pad;
+  const int nt = b->nt;
+  std::vector<double> h((size_t)np * np);
+  HIP_TRY(hipMemcpyAsync(h.data(), b->Ab, sizeof(double) * h.size(), hipMemcpyDeviceToHost,
+                        b->stream));
+  if (nt > 1)
+    HIP_TRY(hipMemcpyAsync(T_out, b->red.Tm, sizeof(double) * (size_t)(nt - 1) * TS * TS,
+                          hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  for (int64_t i = 0; i < np; ++i)
+    for (int64_t j = 0; j < np; ++j) {
+      const int64_t hi = std::max(i, j), lo = std::min(i, j);
+      B_out[i * ld + j] = (hi - lo <= TS) ? h[(size_t)hi * np + lo] : 0.0;
+      V_out[i * ld + j] = 0.0;
+    }
+  // panel j: rows from 128 (j + 1), columns [128 j, +128), unit lower trapezoidal
+  for (int j = 0; j + 1 < nt; ++j) {
+    const int64_t r0 = (int64_t)(j + 1) * TS, c0 = (int64_t)j * TS;
+    for (int64_t i = 0; r0 + i < np; ++i)
+      for (int64_t q = 0; q < TS && q <= i; ++q)
+        V_out[(r0 + i) * ld + c0 + q] = (i == q) ? 1.0 : h[(size_t)(r0 + i) * np + c0 + q];
+  }
+  return 0;
+}
+
+int gpmi_band_get_rhs(gpmi_band* b, double* Y_out, int64_t ld) {
+  if (!b) return set_error(-1006, "null handle");
+  if (!Y_out) return set_error(-1004, "null output");
+  if (b->nrhs <= 0) return set_error(-1204, "no right-hand side is resident");
+  if (ld < b->nrhs) return set_error(-1003, "ld < nrhs");
+  DeviceGuard g(b->device);
+  std::vector<double> h((size_t)b->n_pad * RLD);
+  HIP_TRY(hipMemcpyAsync(h.data(), b->Y, sizeof(double) * h.size(), hipMemcpyDeviceToHost,
+                        b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  for (int64_t i = 0; i < b->n_pad; ++i)
+    for (int c = 0; c < b->nrhs; ++c) Y_out[i * ld + c] = h[(size_t)i * RLD + c];
+  return 0;
+}
+
+int gpmi_band_get_solution(gpmi_band* b, int slot, double* X_out, int64_t ld) {
+  if (!b) return set_error(-1006, "null handle");
+  if (!X_out) return set_error(-1004, "null output");
+  const BandEval& ev = b->eval;
+  if (ev.sol_path == 0 || b->nrhs <= 0)
+    return set_error(-1204, "no solution: gpmi_band_der_terms has not run on this band and RHS");
+  if (slot < 0 || slot >= ev.sol_neta)
+    return set_error(-1205, "slot outside the last gpmi_band_der_terms call");
+  if (ev.sol_info[(size_t)slot] != 0) return set_error(-1206, "that eta's factorization failed");
+  if (ld < b->nrhs) return set_error(-1003, "ld < nrhs");
+  DeviceGuard g(b->device);
+  const int64_t sZ = ev.plan.sZ;
+  const double* src = (ev.sol_path == 1 ? static_cast<const double*>(ev.der.ysol) : static_cast<const double*>(ev.bcr.X)) + (int64_t)slot * sZ;
+  std::vector<double> h((size_t)sZ);
+  HIP_TRY(hipMemcpyAsync(h.data(), src, sizeof(double) * h.size(), hipMemcpyDeviceToHost,
+                        b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  for (int64_t i = 0; i < b->n_pad; ++i)
+    for (int c = 0; c < b->nrhs; ++c) X_out[i * ld + c] = h[(size_t)i * RLD + c];
+  return 0;
+}
+
+int gpmi_band_get_sinv(gpmi_band* b, int slot, int tangent, double* Zd_out, double* Zo_out) {
+  if (!b) return set_error(-1006, "null handle");
+  if (!Zd_out || !Zo_out) return set_error(-1004, "null output");
+  const BandEval& ev = b->eval;
+  if (ev.sinv_neta == 0) return set_error(-1204, "no selected inversion has run on this band");
+  if (tangent && !ev.sinv_tan)
+    return set_error(-1204, "the last selected inversion carried no tangent (exponent 2)");
+  if (slot < 0 || slot >= ev.sinv_neta)
+    return set_error(-1205, "slot outside the last selected-inversion call");
+  DeviceGuard g(b->device);
+  const int nt = b->nt;
+  const size_t blk = (size_t)TS * TS;
+  const double* zd = (tangent ? static_cast<const double*>(ev.tan.Zd) : static_cast<const double*>(ev.sinv.Zd)) + (int64_t)slot * ev.plan.sL;
+  const double* zo = (tangent ? static_cast<const double*>(ev.tan.Zo) : static_cast<const double*>(ev.sinv.Zo)) + (int64_t)slot * ev.plan.sW;
+  HIP_TRY(hipMemcpyAsync(Zd_out, zd, sizeof(double) * nt * blk, hipMemcpyDeviceToHost, b->stream));
+  HIP_TRY(hipMemcpyAsync(Zo_out, zo, sizeof(double) * 2 * nt * blk, hipMemcpyDeviceToHost,
+                        b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
+  // slots no kernel writes: the root's (block 0), and the right one of a level's last
+  // block when that block is odd there
+  for (int o = 0; o < nt; ++o) {
+    int lvl = 0, m = nt;
+    if (o > 0)
+      for (; !((o >> lvl) & 1); ++lvl) m = (m + 1) >> 1;
+    const int p = o >> lvl;
+    for (int side = 0; side < 2; ++side)
+      if (o == 0 || (side == 1 && p + 1 >= m))
+        std::fill_n(Zo_out + ((size_t)o * 2 + side) * blk, blk, 0.0);
+  }
+  return 0;
+}
+
+int gpmi_band_get_tridiagonal(gpmi_band* b, double* d_out, double* e2_out) {
+  if (!b) return set_error(-1006, "null handle");
+  if (!d_out || !e2_out) return set_error(-1004, "null output");
+  if (!b->eig.td_valid) return set_error(-1204, "gpmi_band_eigenvalues has not run on this band");
+  DeviceGuard g(b->device);
+  const int64_t np = b->n_pad, n = b->n;
+  HIP_TRY(hipMemcpyAsync(d_out, b->eig.td, sizeof(double) * n, hipMemcpyDeviceToHost, b->stream));
+  if (n > 1)
+    HIP_TRY(hipMemcpyAsync(e2_out, b->eig.td + np, sizeof(double) * (n - 1), hipMemcpyDeviceToHost,
+                          b->stream));
+  HIP_TRY(hipStreamSynchronize(b->stream));
   return 0;
 }
 

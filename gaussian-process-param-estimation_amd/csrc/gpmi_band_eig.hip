@@ -67,6 +67,7 @@ int gpmi_band_eigenvalues(gpmi_band* b, double* lam) {
   const int64_t np = b->n_pad;
   const int n = (int)b->n;
   HIP_TRY(b->eig.td.reserve(td_doubles(np)));
+  b->eig.td_valid = false;
   double* d = b->eig.td;
   double* e2 = b->eig.td + np;
   double* dl = b->eig.td + 2 * np;
@@ -171,6 +172,7 @@ int gpmi_band_eigenvalues(gpmi_band* b, double* lam) {
   float ms = 0.f;
   HIP_TRY(hipEventElapsedTime(&ms, b->ev0, b->ev1));
   b->eig.eig_ms = ms;
+  b->eig.td_valid = true;
   return 0;
 }
 

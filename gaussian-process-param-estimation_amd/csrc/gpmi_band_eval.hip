@@ -93,6 +93,7 @@ int band_loglik_bcr(gpmi_band* b, int neta, hipStream_t s, bool tan = false) {
   const BandPlan& p = ev.plan;
   const int nt = b->nt;
   const int64_t np = b->n_pad;
+  if (neta > c.cap && ev.sol_path == 2) ev.sol_path = 0;   // X is released with the group
   HIP_TRY(c.reserve(neta, p));
   if (nt > 1) {
     HIP_TRY(ev.F0.reserve((size_t)(nt - 1) * TS * TS));
@@ -212,9 +213,13 @@ int band_sinv_bcr(gpmi_band* b, int neta, hipStream_t s, bool tan = false) {
   const BandPlan& p = b->eval.plan;
   const std::vector<int>& ms = b->eval.levels;
   const int nt = b->nt, L = (int)ms.size();
+  b->eval.sinv_neta = 0;   // (the read-back's bookkeeping: nothing until this call is queued)
+  b->eval.sinv_tan = false;
   HIP_TRY(v.reserve(neta, p));
   const int64_t sZd = p.sL, sZo = p.sW, sX = p.sW;
   const int nt_ = tan ? 1 : 0;
+  b->eval.sinv_neta = neta;
+  b->eval.sinv_tan = tan;
   // every block's X_l, X_r, Linv^T Linv (and tangents), the root's trace
   hipLaunchKernelGGL(bcr_sinv_pre_kernel, dim3(nt * (3 + 3 * nt_), neta), dim3(256), 0, s, c.L,
                      t.L, p.sL, c.W, t.W, p.sW, v.X, t.X, sX, v.Zd, t.Zd, sZd, v.Tr, t.Tr, nt, L,
@@ -247,8 +252,12 @@ int der_terms_chunk(gpmi_band* b, const double* etas, int neta, const EvalOut& o
   const bool tr = o.tr1 || o.tr2, tan = o.tr2 != nullptr;
   HIP_TRY(b->io.reserve(neta));
   HIP_TRY(ev.der.reserve(neta, ev.plan));
-  if (tan) HIP_TRY(ev.tan.reserve(neta, ev.plan));
+  if (tan) {
+    ev.sinv_tan = false;
+    HIP_TRY(ev.tan.reserve(neta, ev.plan));
+  }
   hipStream_t s = b->stream;
+  ev.sol_path = 0;
   int rc = eval_begin(b, etas, neta);
   if (rc) return rc;
   // the traces need the cyclic-reduction factor (the tree they invert along); the
@@ -277,6 +286,15 @@ int der_terms_chunk(gpmi_band* b, const double* etas, int neta, const EvalOut& o
   }
   HIP_TRY(hipEventRecord(b->ev1, s));
   if ((rc = copy_back(b, neta, o))) return rc;
+  // what gpmi_band_get_solution may return (host bookkeeping; the info of a caller
+  // that did not ask for it is read here)
+  ev.sol_info.assign((size_t)neta, 0);
+  if (o.info)
+    std::copy(o.info, o.info + neta, ev.sol_info.begin());
+  else
+    HIP_TRY(hipMemcpy(ev.sol_info.data(), b->io.info, sizeof(int) * neta, hipMemcpyDeviceToHost));
+  ev.sol_neta = neta;
+  ev.sol_path = (tr || use_bcr(b, neta)) ? 2 : 1;
   if ((rc = elapsed_ms(b->ev0, b->ev1, &ev.der_ms))) return rc;
   return tr ? elapsed_ms(b->ev2, b->ev3, &ev.sinv_ms) : 0;
 }
@@ -286,7 +304,10 @@ int traceinv_chunk(gpmi_band* b, const double* etas, int neta, const EvalOut& o)
   BandEval& ev = b->eval;
   const bool tan = o.tr2 != nullptr;
   HIP_TRY(b->io.reserve(neta));
-  if (tan) HIP_TRY(ev.tan.reserve(neta, ev.plan));
+  if (tan) {
+    ev.sinv_tan = false;
+    HIP_TRY(ev.tan.reserve(neta, ev.plan));
+  }
   hipStream_t s = b->stream;
   int rc = eval_begin(b, etas, neta);
   if (rc) return rc;

@@ -199,6 +199,13 @@ struct BandEval {
   BandTan tan;
   BandDer der;
   double sinv_ms = 0.0, der_ms = 0.0;
+  // what the read-backs (gpmi_band_get_solution / _get_sinv) may return: host
+  // bookkeeping of the last der_terms / selected-inversion chunk, cleared by a reduction
+  int sol_path = 0;            // 0 nothing, 1 der.ysol (sequential), 2 bcr.X
+  int sol_neta = 0;
+  std::vector<int> sol_info;   // that chunk's info per eta
+  int sinv_neta = 0;
+  bool sinv_tan = false;       // the tangents dZd, dZo belong to the same chunk
 };
 
 // eigenvalues (bulge chase + bisection), computed on request
@@ -206,6 +213,7 @@ struct BandEig {
   DevBuf<double> Ac;   // [n_pad][n_pad] chase copy of the band (lower), launch form only
   DevBuf<double> td;   // td_doubles(n_pad): diagonal, squared subdiagonal, eigenvalues, slots
   double eig_ms = 0.0;
+  bool td_valid = false;   // td holds the tridiagonal of the current band (read-back)
   // systolic chase (chase_systolic_kernel): one workgroup per position, all
   // co-resident; used when chase_maxg (CU count x resident workgroups per CU)
   // covers the positions, else (and after a timed-out hand-off) the launch form

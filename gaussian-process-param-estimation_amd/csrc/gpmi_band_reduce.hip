@@ -393,6 +393,12 @@ int band_reduce_pass(gpmi_band* b, const double* K, const std::vector<double>* y
 int band_reduce(gpmi_band* b, const double* K, const std::vector<double>* yh) {
   BandReduce& r = b->red;
   int rc;
+  // a new band: what the evaluator and the chase left belongs to the old one
+  b->eval.sol_path = 0;
+  b->eval.sol_neta = 0;
+  b->eval.sinv_neta = 0;
+  b->eval.sinv_tan = false;
+  b->eig.td_valid = false;
   if (r.panel_mode == 0) {
     // a failed CholeskyQR panel is refactored in place (cq_panel); only a timed-out
     // guarded Householder panel (its workgroups not co-resident on a shared GPU)

@@ -16,6 +16,7 @@ _LIB_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), '_lib')
 LIB_PATH = os.path.join(_LIB_DIR, 'libgpmi%s.so' % (
     '_' + os.environ['GPMI_LIB_VARIANT'] if os.environ.get('GPMI_LIB_VARIANT') else ''))
 MAX_RHS = 16
+TS = 128   # GPMI_TS: the tile and band block size
 
 _lib = None
 
@@ -130,6 +131,13 @@ SIGNATURES = {
     'gpmi_band_loglik': (ctypes.c_int, [c_op_p, c_double_p, ctypes.c_int, c_double_p,
                                         c_double_p, c_int_p]),
     'gpmi_band_get': (ctypes.c_int, [c_op_p, c_double_p, c_i64]),
+    'gpmi_band_get_reduction': (ctypes.c_int, [c_op_p, c_double_p, c_double_p, c_double_p,
+                                               c_i64]),
+    'gpmi_band_get_rhs': (ctypes.c_int, [c_op_p, c_double_p, c_i64]),
+    'gpmi_band_get_solution': (ctypes.c_int, [c_op_p, ctypes.c_int, c_double_p, c_i64]),
+    'gpmi_band_get_sinv': (ctypes.c_int, [c_op_p, ctypes.c_int, ctypes.c_int, c_double_p,
+                                          c_double_p]),
+    'gpmi_band_get_tridiagonal': (ctypes.c_int, [c_op_p, c_double_p, c_double_p]),
     'gpmi_band_eigenvalues': (ctypes.c_int, [c_op_p, c_double_p]),
     'gpmi_band_der_terms': (ctypes.c_int, [c_op_p, c_double_p, ctypes.c_int, c_double_p,
                                            c_double_p, c_double_p, c_double_p, c_int_p]),
@@ -827,6 +835,71 @@ class Band(object):
         B = numpy.empty((self.n, self.n))
         check(self.lib.gpmi_band_get(self.h, dptr(B), self.n), 'gpmi_band_get')
         return B
+
+    # Read-backs of what each stage left on the device (tests, diagnostics): copies, no
+    # kernel; GPMIError while what they read does not exist.
+
+    def reduction(self):
+        """-> (B, V, T) of K_pad = Q B Q^T, Q = prod_j (I - V_j T_j V_j^T), all at n_pad
+        size: B symmetric with the pad block as the device holds it, V [n_pad, n_pad]
+        with panel j's unit lower trapezoid in columns [128 j, +128) from row
+        128 (j + 1), T [nt - 1, 128, 128] (gpmi_band_get_reduction)."""
+        npad = self.op.n_pad
+        B = numpy.full((npad, npad), numpy.nan)
+        V = numpy.full((npad, npad), numpy.nan)
+        T = numpy.full((max(npad // TS - 1, 0), TS, TS), numpy.nan)
+        check(self.lib.gpmi_band_get_reduction(self.h, dptr(B), dptr(V), dptr(T), npad),
+              'gpmi_band_get_reduction')
+        return B, V, T
+
+    def rhs(self):
+        """Y = Q^T R of the resident RHS, [n_pad, nrhs] (gpmi_band_get_rhs)."""
+        Y = numpy.full((self.op.n_pad, max(self.nrhs, 1)), numpy.nan)
+        check(self.lib.gpmi_band_get_rhs(self.h, dptr(Y), Y.shape[1]), 'gpmi_band_get_rhs')
+        return Y
+
+    def solution(self, slot=0):
+        """x = (B + eta_slot I)^-1 Y as the last der_terms call (its last chunk) left it,
+        [n_pad, nrhs] (gpmi_band_get_solution)."""
+        X = numpy.full((self.op.n_pad, max(self.nrhs, 1)), numpy.nan)
+        check(self.lib.gpmi_band_get_solution(self.h, int(slot), dptr(X), X.shape[1]),
+              'gpmi_band_get_solution')
+        return X
+
+    def sinv_raw(self, slot=0, tangent=False):
+        """-> (Zd [nt, 128, 128], Zo [nt, 2, 128, 128]) of the last selected inversion by
+        original block index, as stored (tangent: dZd, dZo); unused Zo slots are zero
+        (gpmi_band_get_sinv)."""
+        nt = self.op.n_pad // TS
+        Zd = numpy.full((nt, TS, TS), numpy.nan)
+        Zo = numpy.full((nt, 2, TS, TS), numpy.nan)
+        check(self.lib.gpmi_band_get_sinv(self.h, int(slot), int(bool(tangent)), dptr(Zd),
+                                          dptr(Zo)), 'gpmi_band_get_sinv')
+        return Zd, Zo
+
+    def sinv_blocks(self, slot=0, tangent=False):
+        """-> (diag [nt, 128, 128], sub [nt - 1, 128, 128]): the block-tridiagonal part
+        of Z = (B + eta_slot I)^-1 (tangent: of dZ / d eta) in original order,
+        diag[k] = Z_kk and sub[k] = Z_{k+1,k}. The cyclic reduction eliminates the odd
+        blocks k at level 0, whose Z_{k-1,k} and Z_{k+1,k} are Zo[k][0] and Zo[k][1]; an
+        even k takes the transposes from its odd neighbours."""
+        Zd, Zo = self.sinv_raw(slot, tangent)
+        nt = Zd.shape[0]
+        sub = numpy.empty((max(nt - 1, 0), TS, TS))
+        for k in range(nt - 1):
+            # Z_{k+1,k}: k odd: its own right block; k even: (Z_{k,k+1})^T of odd k + 1
+            sub[k] = Zo[k, 1] if k % 2 == 1 else Zo[k + 1, 0].T
+        return Zd, sub
+
+    def tridiagonal(self):
+        """-> (d [n], e2 [n - 1]): the diagonal and squared subdiagonal the bulge chase
+        left, which the bisection of the last eigenvalues() read
+        (gpmi_band_get_tridiagonal)."""
+        d = numpy.full(self.n, numpy.nan)
+        e2 = numpy.full(max(self.n - 1, 1), numpy.nan)
+        check(self.lib.gpmi_band_get_tridiagonal(self.h, dptr(d), dptr(e2)),
+              'gpmi_band_get_tridiagonal')
+        return d, e2[:self.n - 1]
 
     def last_timing(self):
         a, b, c = ctypes.c_double(), ctypes.c_double(), ctypes.c_double()

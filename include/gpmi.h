@@ -625,6 +625,39 @@ int gpmi_band_eigenvalues(gpmi_band* b, double* lam);
 /* The band matrix B as a dense symmetric [n][ld] host matrix (tests). */
 int gpmi_band_get(gpmi_band* b, double* B_out, int64_t ld);
 
+/* Read-backs of what each stage of the band path left on the device (tests and
+ * diagnostics; tests/test_gpu_band_stages.py holds each to a backward-error bar). Each is
+ * a copy on the handle's stream: no kernel runs and no later result changes. While what
+ * one reads does not exist it returns -1204; a slot outside the last call -1205; a slot
+ * whose factorization failed -1206; a leading dimension too small -1003; a null output
+ * -1004. No reference counterpart.
+ *
+ * The reduction K_pad = Q B Q^T, Q = prod_j (I - V_j T_j V_j^T) over the nt - 1 panels
+ * (nt = n_pad / 128), everything at n_pad size: B_out [n_pad][ld] symmetric (the stored
+ * lower band mirrored, as gpmi_band_get, the pad block as the device holds it: the
+ * identity); V_out [n_pad][ld] with panel j's unit lower trapezoid in columns
+ * [128 j, +128) and rows from 128 (j + 1), the unit diagonal written, zero elsewhere;
+ * T_out [nt - 1][128][128] the compact-WY T of every panel as stored. ld >= n_pad. */
+int gpmi_band_get_reduction(gpmi_band* b, double* B_out, double* V_out, double* T_out,
+                            int64_t ld);
+/* Y = Q^T R of the resident RHS, Y_out [n_pad][ld], nrhs columns written. */
+int gpmi_band_get_rhs(gpmi_band* b, double* Y_out, int64_t ld);
+/* x = (B + eta_slot I)^-1 Y as the last gpmi_band_der_terms(_ex, _ex2) call left it
+ * (the sequential kernel's or the cyclic reduction's, whichever ran), X_out [n_pad][ld],
+ * nrhs columns written. slot counts within that call's last device chunk (a call with
+ * tr2 runs in chunks of GPMI_BAND_TAN_MAX). A new RHS or reduction discards it. */
+int gpmi_band_get_solution(gpmi_band* b, int slot, double* X_out, int64_t ld);
+/* The blocks of (B + eta_slot I)^-1 the last selected inversion (gpmi_band_traceinv,
+ * _traceinv2, _der_terms_ex, _ex2 with tr1; its last chunk) left, by original block
+ * index o: Zd_out [nt][128][128] = Z_oo; Zo_out [nt][2][128][128] = Z_lo, Z_ro for
+ * the neighbours l, r of o at the level that eliminated it (level 0: o - 1 and o + 1 for
+ * odd o); slots no neighbour fills are zeroed. tangent = 1: the eta-derivatives dZd,
+ * dZo, present after a call with tr2. */
+int gpmi_band_get_sinv(gpmi_band* b, int slot, int tangent, double* Zd_out, double* Zo_out);
+/* The tridiagonal the last gpmi_band_eigenvalues' bulge chase left and its bisection
+ * read: d_out [n] the diagonal, e2_out [n - 1] the squared subdiagonal. */
+int gpmi_band_get_tridiagonal(gpmi_band* b, double* d_out, double* e2_out);
+
 /* Device ms of the last reduction, Q^T application and loglik call (HIP events). */
 int gpmi_band_last_timing(gpmi_band* b, double* reduce_ms, double* rhs_ms,
                           double* loglik_ms);

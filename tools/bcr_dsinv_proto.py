@@ -76,7 +76,8 @@ def bcr_factor_tan(D, F):
     return Linv, dLinv, W, dW, ms, lvl
 
 
-def sinv_tan(Linv, dLinv, W, dW, ms, L):
+def sinv_tan(Linv, dLinv, W, dW, ms, L, want_blocks=False):
+    """-> (tr1, tr2, dZd); want_blocks: (Zd, Zo, dZd, dZo) by original block index."""
     nt = len(Linv)
     Zd, dZd = [None] * nt, [None] * nt
     Zo = [[None, None] for _ in range(nt)]
@@ -114,6 +115,8 @@ def sinv_tan(Linv, dLinv, W, dW, ms, L):
                 Zo[o], dZo[o] = [Zlp, None], [dZlp, None]
                 Zd[o] = Li.T @ Li - Xl.T @ Zlp
                 dZd[o] = dLi.T @ Li + Li.T @ dLi - dXl.T @ Zlp - Xl.T @ dZlp
+    if want_blocks:
+        return Zd, Zo, dZd, dZo
     return (sum(np.trace(z) for z in Zd), -sum(np.trace(z) for z in dZd), dZd)
 
 

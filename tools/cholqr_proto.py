@@ -65,14 +65,22 @@ def cholqr_panel(P, shifted_passes=1, passes=3, first_order=True):
     return (V, tau, Rhh), info
 
 
-def band_reduce_cholqr(K, b, stats):
+def band_reduce_cholqr(K, b, stats, n_real=None, want_vt=False, first_order=True):
+    """-> the reduced matrix (want_vt: and every panel's V and T). n_real: K is an
+    n_real matrix padded by the identity; a last panel with fewer than b real rows has
+    rank < b and goes to the Householder panel, as on the device (panel_qr)."""
     A = numpy.tril(K).copy()
     A = A + numpy.tril(A, -1).T
     n = A.shape[0]
+    n_real = n if n_real is None else n_real
+    Vs, Ts = [], []
     for j in range(n // b - 1):
         r0, c0 = (j + 1) * b, j * b
         P = A[r0:, c0:c0 + b]
-        out, info = cholqr_panel(P)
+        if n_real - r0 >= b:
+            out, info = cholqr_panel(P, first_order=first_order)
+        else:
+            out, info = None, {'ragged': True}
         if out is None:
             tau = householder_panel(P)
             V = v_of(P)
@@ -90,7 +98,9 @@ def band_reduce_cholqr(K, b, stats):
         A22 -= W @ V.T + V @ W.T
         # keep the band only (the panel's entries below R are the reflectors' zeros)
         A[c0:c0 + b, r0:] = A[r0:, c0:c0 + b].T
-    return A
+        Vs.append(V.copy())
+        Ts.append(T)
+    return (A, Vs, Ts) if want_vt else A
 
 
 def main():
