@@ -139,6 +139,22 @@ void launch_scale_grad_pass(hipStream_t s, int mode, int nc, const double* W, in
 __global__ void scale_grad_reduce_kernel(const double* part, int ntile, int nval, int d,
                                          const double* scale_dev, double* out);
 
+// Second-order (expected information) terms (gpmi_fisher.hip): M_k = A^-1 dK / d rho_k on
+// fp64 MFMA into M[d][np][np], the traces tr(M_a M_b) tile by tile and reduced in a fixed
+// order, the thin products with [np][16] blocks and their 16 x 16 Grams. a = 0 stands for
+// A^-1 itself, read from the tiles (W, Td) with the pad masked.
+void launch_fisher_product(hipStream_t s, int mode, const double* W, int64_t np, const double* Td,
+                           const double* points, int64_t n, int d, const double* scale, int nt,
+                           double* M);
+__global__ void fisher_trace_kernel(const double* M, int64_t np, const double* W,
+                                    const double* Td, int64_t n, int d, int nt, double* part);
+__global__ void fisher_trace_reduce_kernel(const double* part, int ntile, double* out);
+__global__ void fisher_copy_sol_kernel(const double* sol, int64_t np, double* Y0);
+void launch_fisher_thin(hipStream_t s, bool trans, int a0, int count, const double* M, int64_t np,
+                        const double* W, const double* Td, int64_t n, const double* X, int ldx,
+                        double* out);
+__global__ void fisher_gram_kernel(const double* YZ, int64_t np, int d, double* out);
+
 // Draws from the cached factor and the covariance hand-over (gpmi_sample.hip; work list in
 // gpmi_sample_plan.h).
 __global__ void sample_normal_kernel(double* Xi, int64_t ld, int64_t rows, int64_t cols,

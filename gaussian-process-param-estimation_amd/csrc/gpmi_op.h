@@ -10,6 +10,7 @@
 //   gpmi_dense_predict.hip  the prediction terms and the joint covariance (DensePredict)
 //   gpmi_dense_loo.hip      the leave-one-out terms (DenseLoo)
 //   gpmi_dense_scale_grad.hip  the correlation-scale gradient terms (DenseScaleGrad)
+//   gpmi_dense_fisher.hip   the second-order terms of the expected information (DenseFisher)
 //   gpmi_dense_sample.hip   draws from the cached factor, and the hand-over of the joint
 //                           covariance to a second operator (DenseSample)
 // Every device buffer is a DevBuf, every stream and event an owner (gpmi_host.h):
@@ -94,6 +95,7 @@ struct DenseTiming {
   EventPool cov;           // begin, end of the covariance's partial-product launch
   EventPool loo;           // begin, end of the leave-one-out pass over W
   EventPool sgrad;         // begin, end of the scale gradient's pass over the tiles of A^-1
+  EventPool fisher;        // begin of the call, begin and end of the product stage, end of the call
   EventPool samp;          // per chunk of draws: begin, end of the normals and of the product
   std::vector<std::pair<int, double>> syrk_log;  // (event index, flops)
   std::vector<std::array<int, 3>> syrk_shape;    // (w, t, kdim) per logged launch
@@ -152,6 +154,18 @@ struct DenseScaleGrad {
   double last_ms = 0.0, last_bytes = 0.0;
 };
 
+// gpmi_op_fisher_terms: the points and scale of the call on the device, the d products
+// M_k = A^-1 dK / d rho_k, the thin blocks and the partials (grown to the largest call so far).
+struct DenseFisher {
+  DevBuf<double> pts;      // [n][d]
+  DevBuf<double> scale;    // [8]
+  DevBuf<double> M;        // [d][n_pad][n_pad]
+  DevBuf<double> YZ;       // [2][d + 1][n_pad][16] Y_a = N_a S, then Z_a = A^-1 Y_a
+  DevBuf<double> part;     // [(d + 1)(d + 2) / 2][nt * nt] per-tile partials of the traces
+  DevBuf<double> out;      // [(d + 1)(d + 2) / 2] traces, then [(d + 1) + (d + 1)^2][16][16] Grams
+  double last_product_ms = 0.0, last_total_ms = 0.0;
+};
+
 // gpmi_op_sample / gpmi_op_load_predict_cov: workspace of one chunk of draws, grown to
 // the largest so far (sizes and work list: gpmi_sample_plan.h).
 struct DenseSample {
@@ -193,6 +207,7 @@ struct gpmi_op {
   gpmi::DensePredict pred;
   gpmi::DenseLoo loo;
   gpmi::DenseScaleGrad sgrad;
+  gpmi::DenseFisher fisher;
   gpmi::DenseSample samp;
 
   gpmi::BatchPtrs ptrs() const { return fac.ptrs(n_pad, nt); }

@@ -80,6 +80,10 @@ SIGNATURES = {
                                                 c_double_p, ctypes.c_int, c_double_p,
                                                 c_double_p]),
     'gpmi_op_scale_grad_ms': (ctypes.c_int, [c_op_p, c_double_p, c_double_p]),
+    'gpmi_op_fisher_terms': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p, ctypes.c_int,
+                                            c_double_p, ctypes.c_double, c_double_p,
+                                            c_double_p, c_double_p]),
+    'gpmi_op_fisher_ms': (ctypes.c_int, [c_op_p, c_double_p, c_double_p]),
     'gpmi_op_predict_cov_resident': (ctypes.c_int, [c_op_p, ctypes.c_double, c_double_p,
                                                     ctypes.c_int, c_double_p, ctypes.c_double,
                                                     c_double_p, c_i64, c_double_p, c_i64,
@@ -640,6 +644,39 @@ class Operator(object):
         check(self.lib.gpmi_op_scale_grad_ms(self.h, ctypes.byref(a), ctypes.byref(b)),
               'gpmi_op_scale_grad_ms')
         return dict(pass_ms=a.value, pass_bytes=b.value)
+
+    def fisher_terms(self, eta, points, scale, nu):
+        """-> (T[d + 1, d + 1], U[d + 1, s, s], V[d + 1, d + 1, s, s]) for the factor of
+        A = K + eta I, K the Matérn correlation of ``points`` (n x d) at ``scale`` (d) and
+        ``nu``, and the s resident RHS columns R: with N_0 = I, N_k = dK/d rho_k,
+        S = A^-1 R, M_0 = A^-1, M_k = A^-1 N_k and Y_a = N_a S,
+        T[a, b] = tr(M_a M_b) (exactly symmetric), U[a] = S^T Y_a, V[a, b] = Y_a^T A^-1 Y_b
+        (gpmi_op_fisher_terms): the d products M_k on fp64 MFMA from the tiles of A^-1 that
+        traceinv(eta, 2) forms and caches. nu must be 0.5, 1.5, 2.5 or >= 100."""
+        points = as_c(points)
+        scale = as_c(scale)
+        if points.ndim != 2 or points.shape[0] != self.n:
+            raise ValueError('points must be %d x d' % self.n)
+        d = points.shape[1]
+        if scale.shape != (d,):
+            raise ValueError('scale must have one entry per dimension (%d)' % d)
+        s = self.nrhs
+        T = numpy.zeros((d + 1, d + 1))
+        U = numpy.zeros((d + 1, s, s))
+        V = numpy.zeros((d + 1, d + 1, s, s))
+        check(self.lib.gpmi_op_fisher_terms(self.h, float(eta), dptr(points), d, dptr(scale),
+                                            float(nu), dptr(T), dptr(U), dptr(V)),
+              'gpmi_op_fisher_terms')
+        return T, U, V
+
+    def fisher_ms(self):
+        """-> dict(product_ms, total_ms): the product stage (the d products M_k) and the
+        whole device side of the last fisher_terms with set_timing(True) (HIP events; 0
+        without)."""
+        a, b = ctypes.c_double(), ctypes.c_double()
+        check(self.lib.gpmi_op_fisher_ms(self.h, ctypes.byref(a), ctypes.byref(b)),
+              'gpmi_op_fisher_ms')
+        return dict(product_ms=a.value, total_ms=b.value)
 
 
 class Band(object):

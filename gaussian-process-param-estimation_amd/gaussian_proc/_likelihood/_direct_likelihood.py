@@ -28,7 +28,7 @@ import numpy
 import scipy.optimize
 from functools import partial
 
-from ._profile_likelihood import _use_band, _scale_grad_from_terms
+from ._profile_likelihood import _use_band, _scale_grad_from_terms, _fisher_from_terms
 
 __all__ = ['DirectLikelihood']
 
@@ -238,6 +238,24 @@ class DirectLikelihood(object):
         n, m = X.shape
         T = K_mixed.scale_grad_terms((sigma0 / sigma) ** 2, X, z, **kernel_params)
         return _scale_grad_from_terms(n, m, T['t'], T['qX'], T['qc'], T['G'], sigma=sigma)
+
+    @staticmethod
+    def fisher_information(z, X, K_mixed, hyperparam, **kernel_params):
+        """The expected information of the direct (restricted) likelihood at
+        ``hyperparam = (sigma, sigma0)`` in theta = (sigma, sigma0, rho_1 .. rho_d), rho
+        the correlation scale of K: I_ab = tr(P_S S_a P_S S_b) / 2, analytic, from one
+        factorization and the device's second-order terms (MixedCorrelation.fisher_terms,
+        _fisher_from_terms). It does not depend on z, which only fills the resident
+        block. |sigma| below the small-sigma threshold raises ValueError.
+        ``kernel_params``: points, correlation_scale and nu for an ndarray K.
+        -> array (d + 2, d + 2), symmetric."""
+        sigma, sigma0 = float(hyperparam[0]), float(hyperparam[1])
+        if numpy.abs(sigma) < _TOL:
+            raise ValueError('the information needs |sigma| >= %g' % _TOL)
+        X = numpy.asarray(X, dtype=float)
+        n, m = X.shape
+        T = K_mixed.fisher_terms((sigma0 / sigma) ** 2, X, z, **kernel_params)
+        return _fisher_from_terms(n, m, sigma, sigma0, T)
 
     @staticmethod
     def log_likelihood_hessian(z, X, K_mixed, sign_switch, hyperparam):    # :163-270

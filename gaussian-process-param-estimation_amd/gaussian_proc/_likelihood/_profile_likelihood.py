@@ -201,6 +201,59 @@ def _eta_grad_from_terms(n, m, trinv, sol, G):
     return -0.5 * trP + 0.5 * (n - m) * float(w @ w) / float(c @ G @ c)
 
 
+def _fisher_from_terms(n, m, sigma, sigma0, terms):
+    """The expected information of the restricted likelihood in
+    theta = (sigma, sigma0, rho_1 .. rho_d) from the terms of
+    MixedCorrelation.fisher_terms: I_ab = tr(P_S S_a P_S S_b) / 2 with
+    S = sigma^2 K + sigma0^2 I = sigma^2 A, S_a = dS / d theta_a and P_S = P / sigma^2 its
+    REML projector, P = A^-1 - A^-1 X B^-1 X^T A^-1, B = X^T A^-1 X = G_XX. With
+    eta = (sigma0 / sigma)^2, N_0 = I, N_k = dK / d rho_k, and from the X part of U, V
+    (the expected information does not depend on z)
+      p_ab  = tr(P N_a P N_b) = T_ab - 2 tr(B^-1 V_ab) + tr(B^-1 U_a B^-1 U_b)
+      tau_a = tr(P N_a)       = (trinv | t_a) - tr(B^-1 U_a),
+    the derivatives S_sigma = 2 sigma (A - eta I), S_sigma0 = 2 sigma0 I,
+    S_rho_k = sigma^2 N_k and P A P = P, tr(P A) = n - m give
+      I[sigma, sigma]   = 2 ((n - m) - 2 eta tau_0 + eta^2 p_00) / sigma^2
+      I[sigma, sigma0]  = 2 sigma0 (tau_0 - eta p_00) / sigma^3
+      I[sigma0, sigma0] = 2 sigma0^2 p_00 / sigma^4
+      I[sigma, rho_k]   = (tau_k - eta p_0k) / sigma
+      I[sigma0, rho_k]  = sigma0 p_0k / sigma^2
+      I[rho_k, rho_l]   = p_kl / 2.
+    -> array (d + 2, d + 2), symmetrised."""
+    T = numpy.asarray(terms['T'], dtype=float)
+    U = numpy.asarray(terms['U'], dtype=float)
+    V = numpy.asarray(terms['V'], dtype=float)
+    t = numpy.asarray(terms['t'], dtype=float)
+    G = numpy.asarray(terms['G'], dtype=float)
+    d1 = T.shape[0]
+    if T.shape != (d1, d1) or d1 < 1 or t.shape != (d1 - 1,) or G.shape != (m + 1, m + 1) \
+            or U.shape != (d1, m + 1, m + 1) or V.shape != (d1, d1, m + 1, m + 1):
+        raise ValueError('T must be (d + 1) x (d + 1), t d, G (m + 1) x (m + 1), U (d + 1) and '
+                         'V (d + 1) x (d + 1) blocks of G\'s shape')
+    sigma, sigma0 = float(sigma), float(sigma0)
+    if not abs(sigma) > 0.0:
+        raise ValueError('sigma must be non-zero')
+    eta = (sigma0 / sigma) ** 2
+    tau = numpy.concatenate([[float(terms['trinv'])], t])
+    p = T.copy()
+    if m > 0:
+        Bi = numpy.linalg.inv(G[:m, :m])
+        Bi = 0.5 * (Bi + Bi.T)
+        BU = numpy.array([Bi @ U[a, :m, :m] for a in range(d1)])
+        for a in range(d1):
+            tau[a] -= numpy.trace(BU[a])
+            for b in range(d1):
+                p[a, b] += -2.0 * numpy.sum(Bi * V[a, b, :m, :m]) + numpy.sum(BU[a] * BU[b].T)
+    info = numpy.empty((d1 + 1, d1 + 1))
+    info[0, 0] = 2.0 * ((n - m) - 2.0 * eta * tau[0] + eta ** 2 * p[0, 0]) / sigma ** 2
+    info[0, 1] = info[1, 0] = 2.0 * sigma0 * (tau[0] - eta * p[0, 0]) / sigma ** 3
+    info[1, 1] = 2.0 * sigma0 ** 2 * p[0, 0] / sigma ** 4
+    info[0, 2:] = info[2:, 0] = (tau[1:] - eta * p[0, 1:]) / sigma
+    info[1, 2:] = info[2:, 1] = sigma0 * p[0, 1:] / sigma ** 2
+    info[2:, 2:] = 0.5 * p[1:, 1:]
+    return 0.5 * (info + info.T)
+
+
 def _cross_validation_scores(z, mean, var):
     """The summary scores of GaussianProcess.cross_validate from the leave-one-out
     mean and (noisy) variance. -> dict."""

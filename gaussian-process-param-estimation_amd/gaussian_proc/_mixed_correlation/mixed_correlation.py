@@ -828,8 +828,21 @@ class MixedCorrelation(object):
         numpy.linalg.LinAlgError. Returns dict(t, qX, qc, trinv = tr(A^-1) as the sum of
         the leave-one-out pass's diagonal, sol, G)."""
         from .._likelihood._profile_likelihood import _scale_grad_coef
+        X, points, correlation_scale, nu = self._scale_args(
+            X, points, correlation_scale, nu, 'the scale gradient')
+        self.set_rhs(X, z)
+        dinv, sol, G = self.op.loo_terms(eta)
+        t, q = self.op.scale_grad_terms(eta, points, correlation_scale, nu,
+                                        _scale_grad_coef(G))
+        return {'t': t, 'qX': q[0], 'qc': q[1], 'trinv': float(numpy.sum(dinv)), 'sol': sol,
+                'G': G}
+
+    def _scale_args(self, X, points, correlation_scale, nu, what):
+        """X and the kernel parameters of scale_grad_terms / fisher_terms, resolved (a
+        DeviceCorrelation K supplies what is not given) and checked. -> (X, points,
+        correlation_scale, nu)."""
         if self.sparse:
-            raise NotImplementedError('the scale gradient on a sparse K is not implemented')
+            raise NotImplementedError('%s on a sparse K is not implemented' % what)
         X = numpy.asarray(X, dtype=float)
         if X.ndim != 2 or X.shape[0] != self.n:
             raise ValueError('X must be %d x m' % self.n)
@@ -851,13 +864,35 @@ class MixedCorrelation(object):
                              'dimension (%d)' % points.shape[1])
         nu = float(nu)
         if nu not in (0.5, 1.5, 2.5) and nu < 100.0:
-            raise NotImplementedError('the scale gradient needs nu = 0.5, 1.5, 2.5 or >= 100 '
-                                      '(got %g)' % nu)
+            raise NotImplementedError('%s needs nu = 0.5, 1.5, 2.5 or >= 100 (got %g)'
+                                      % (what, nu))
+        return X, points, correlation_scale, nu
+
+    def fisher_terms(self, eta, X, z, points=None, correlation_scale=None, nu=None):
+        """The device terms of the expected (restricted) information in
+        (sigma, sigma0, rho) of a Matérn K (the reference has no counterpart). With
+        A = K + eta I, R = [X z], S = A^-1 R, N_0 = I, N_k = dK / d rho_k, M_0 = A^-1,
+        M_k = A^-1 N_k and Y_a = N_a S, a, b = 0..d:
+          T[a, b] = tr(M_a M_b)     U[a] = S^T Y_a     V[a, b] = Y_a^T A^-1 Y_b
+          t[k]    = tr(A^-1 N_k)    trinv = tr(A^-1)   sol = S    G = R^T S.
+        On the cached Cholesky of A, the tiles of A^-1 and S of scale_grad_terms: the d
+        products M_k are n^3 work each on fp64 MFMA with N_k generated from the point
+        coordinates (csrc/gpmi_fisher.hip), and stay on the device (d n_pad^2 doubles);
+        _fisher_from_terms turns the terms into the information matrix. Kernel
+        parameters resolve and are checked exactly as in scale_grad_terms. Returns
+        dict(T, U, V, t, trinv, sol, G); t, trinv, sol and G are bit for bit those of
+        scale_grad_terms."""
+        from .._likelihood._profile_likelihood import _scale_grad_coef
+        X, points, correlation_scale, nu = self._scale_args(
+            X, points, correlation_scale, nu, 'the information')
         self.set_rhs(X, z)
         dinv, sol, G = self.op.loo_terms(eta)
-        t, q = self.op.scale_grad_terms(eta, points, correlation_scale, nu,
+        # (the call scale_grad_terms makes, coefficient matrices included: the same
+        # instantiation of the pass, so t is its t bit for bit)
+        t, _ = self.op.scale_grad_terms(eta, points, correlation_scale, nu,
                                         _scale_grad_coef(G))
-        return {'t': t, 'qX': q[0], 'qc': q[1], 'trinv': float(numpy.sum(dinv)), 'sol': sol,
+        T, U, V = self.op.fisher_terms(eta, points, correlation_scale, nu)
+        return {'T': T, 'U': U, 'V': V, 't': t, 'trinv': float(numpy.sum(dinv)), 'sol': sol,
                 'G': G}
 
     def sample(self, eta, size=1, seed=0, first=0, xi=None):

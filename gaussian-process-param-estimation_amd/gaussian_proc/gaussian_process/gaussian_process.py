@@ -59,6 +59,71 @@ class GaussianProcess(object):
         return DirectLikelihood.log_likelihood_der1_scale(z, X, self.likelihood.K_mixed,
                                                           hyperparam, **kernel_params)
 
+    def fisher_information(self, z=None, hyperparam=None, **kernel_params):
+        """The expected information of the (direct, restricted) likelihood at
+        ``hyperparam = (sigma, sigma0)`` in theta = (sigma, sigma0, rho_1 .. rho_d), rho
+        the correlation scale of K (DirectLikelihood.fisher_information): how well the
+        data determine the fitted numbers, and the matrix of a Fisher-scoring step. ``z``
+        and ``hyperparam`` default to those of the last ``train`` or ``train_scale``; an
+        ndarray K needs ``points``, ``correlation_scale`` and ``nu`` as keywords.
+        -> array (d + 2, d + 2), symmetric."""
+        from .._likelihood._direct_likelihood import DirectLikelihood
+        if z is None:
+            z = self.z
+        if hyperparam is None and self.results is not None:
+            hyperparam = (self.results['sigma'], self.results['sigma0'])
+        if z is None or hyperparam is None:
+            raise ValueError('fisher_information needs z and hyperparam=(sigma, sigma0), or an '
+                             'earlier train(z)')
+        bad = sorted(set(kernel_params) - {'points', 'correlation_scale', 'nu'})
+        if bad:
+            raise TypeError('fisher_information: unexpected keyword argument %s'
+                            % ', '.join(map(repr, bad)))
+        X = numpy.asarray(self.X, dtype=float)
+        z = numpy.asarray(z, dtype=float)
+        if z.shape != (X.shape[0],):
+            raise ValueError('z must have %d entries' % X.shape[0])
+        return DirectLikelihood.fisher_information(z, X, self.likelihood.K_mixed, hyperparam,
+                                                   **kernel_params)
+
+    def hyperparam_covariance(self, z=None, hyperparam=None, **kernel_params):
+        """The asymptotic covariance of the estimates of (sigma, sigma0, rho_1 .. rho_d):
+        the inverse of ``fisher_information`` (same arguments). An information that is
+        singular to working precision raises numpy.linalg.LinAlgError naming the cause:
+        sigma0 = 0, where the likelihood is even in sigma0 and its row of the
+        information is zero, or parameters the data do not separate.
+        -> array (d + 2, d + 2), symmetric."""
+        info = self.fisher_information(z=z, hyperparam=hyperparam, **kernel_params)
+        names = ['sigma', 'sigma0'] + ['correlation_scale[%d]' % k
+                                       for k in range(info.shape[0] - 2)]
+        diag = numpy.diag(info)
+        if not numpy.all(numpy.isfinite(info)):
+            raise numpy.linalg.LinAlgError('the information is not finite')
+        if numpy.any(diag <= 0.0):
+            k = int(numpy.argmin(diag))
+            why = ' (sigma0 = 0: the likelihood is even in sigma0, so its first derivative ' \
+                  'carries no information there)' if k == 1 else ''
+            raise numpy.linalg.LinAlgError('the information is singular: the data hold no '
+                                           'information on %s%s' % (names[k], why))
+        # in correlation form, so that the parameters' units do not decide the verdict
+        s = 1.0 / numpy.sqrt(diag)
+        w, Q = numpy.linalg.eigh(info * numpy.outer(s, s))
+        if w[0] <= info.shape[0] * numpy.finfo(float).eps * w[-1]:
+            worst = names[int(numpy.argmax(numpy.abs(Q[:, 0])))]
+            raise numpy.linalg.LinAlgError('the information is singular to working precision: '
+                                           'the data do not separate %s from the other '
+                                           'parameters' % worst)
+        cov = (Q / w) @ Q.T * numpy.outer(s, s)
+        return 0.5 * (cov + cov.T)
+
+    def standard_errors(self, z=None, hyperparam=None, **kernel_params):
+        """The asymptotic standard errors of the estimates, the square roots of the
+        diagonal of ``hyperparam_covariance`` (same arguments)
+        -> dict(sigma, sigma0, correlation_scale (d))."""
+        se = numpy.sqrt(numpy.diag(self.hyperparam_covariance(z=z, hyperparam=hyperparam,
+                                                              **kernel_params)))
+        return {'sigma': float(se[0]), 'sigma0': float(se[1]), 'correlation_scale': se[2:]}
+
     def train_scale(self, z, correlation_scale0=None, eta0=1.0, bounds=None, maxiter=100,
                     tol=1e-6):
         """Fit the correlation scale rho (one entry per point dimension) together with

@@ -268,6 +268,39 @@ int gpmi_op_scale_grad_terms(gpmi_op* op, double eta, const double* points, int 
  * read (when gpmi_op_set_timing is on). */
 int gpmi_op_scale_grad_ms(gpmi_op* op, double* pass_ms, double* pass_bytes);
 
+/* ------------------------------------------------------ expected information --
+ * Like the prediction, an extension beyond the reference; serves
+ * gaussian_proc.GaussianProcess.fisher_information, hyperparam_covariance and
+ * standard_errors of this build. */
+
+/* The second-order terms of the likelihood in (sigma, sigma0, rho) of a Matérn K,
+ * from the cached factor of A = K + eta I (factorized if absent) and the resident
+ * RHS block R (s = nrhs columns). With N_0 = I, N_k = dK / d rho_k (k = 1..d, as in
+ * gpmi_op_scale_grad_terms), S = A^-1 R, M_0 = A^-1, M_k = A^-1 N_k and Y_a = N_a S:
+ *   T_out[a * (d + 1) + b]             = tr(M_a M_b)        exactly symmetric
+ *   U_out[a][s][s]                     = S^T Y_a
+ *   V_out[a * (d + 1) + b][s][s]       = Y_a^T A^-1 Y_b
+ * for a, b = 0..d. The d products M_k run on fp64 MFMA: A^-1 is read from the lower
+ * tiles gpmi_op_traceinv(.., 2) forms and caches (the upper part as the mirror),
+ * N_k is generated slab by slab from points[n][d], scale[d] and nu, which must be
+ * those K was assembled with, and is never stored. The traces are summed per tile
+ * and the tiles in a fixed order, the thin products and Grams run in ascending row
+ * order (no atomics: the same input gives the same bits). The call keeps
+ * d n_pad^2 + 32 (d + 1) n_pad doubles (and O(d^2 (n_pad / 128)^2) of partials) of its
+ * own on the device, n_pad = n rounded up to 128, and changes no other cache. Any
+ * output may be NULL. nu must be 0.5, 1.5, 2.5 or >= 100.
+ * > 0: first non-positive pivot; < 0: null handle (-1006), no matrix (-1000), no
+ * resident RHS (-1012), d outside 1..8 (-1003), a null argument (-1004), a general
+ * nu (-1031), no device memory for the call's own buffers (-1032: they are reserved
+ * after the factor, W, the tiles of A^-1 and Sol exist, which stay cached; none of
+ * the terms was computed and the handle stays usable). */
+int gpmi_op_fisher_terms(gpmi_op* op, double eta, const double* points, int d,
+                         const double* scale, double nu, double* T_out, double* U_out,
+                         double* V_out);
+/* HIP-event ms of the last call's product stage (the d products M_k, 2 n_pad^3 d
+ * flops) and of the whole call on the device (when gpmi_op_set_timing is on). */
+int gpmi_op_fisher_ms(gpmi_op* op, double* product_ms, double* total_ms);
+
 /* ---------------------------------------------------------------- sampling --
  * Like the prediction, an extension beyond the reference; serves
  * gaussian_proc.GaussianProcess.sample and MixedCorrelation.sample of this build. */
